@@ -23,6 +23,11 @@ train_apex.py:124-155 / train_r2d2.py:122-162). R2D2 defaults to the
 BASELINE shape seq_len=80 / burn_in=40 (config #4); --seq-len 15
 --burn-in 7 reproduces the reference config.json:88-101 shape.
 
+A plain run does only what the headline figure needs: setup, warmup, the
+timed steps, the result line. --dump-outputs DIR additionally writes what the
+last timed step computed (for build-vs-build comparison); --full is where
+any secondary measurement belongs.
+
 Launch (driver contract):
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -82,13 +87,101 @@ def parse_args(argv):
                         "measure boost-clock steady state, not DVFS ramp")
     p.add_argument("--step-times", action="store_true",
                    help="print per-step GPU ms to stderr (diagnostics)")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the LAST timed "
+                        "step computed (losses, updated parameters, "
+                        "gradients) as DIR/<name>.npy (float32). That "
+                        "step is made to start from the freshly seeded "
+                        "training state on a fixed batch, so two runs with "
+                        "the same arguments agree output for output to "
+                        "rounding (--algo impala only)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement/check the "
+                        "benchmark carries besides its headline figure. A "
+                        "plain run does setup, warmup, the timed steps and "
+                        "the result line only; anything beyond that belongs "
+                        "behind this flag (currently there is none)")
+    args = p.parse_args(argv)
+    if args.dump_outputs and args.algo != "impala":
+        p.error("--dump-outputs is implemented for --algo impala only")
+    return args
 
 
-def run_timed(step, args, world: int, have_gpu: bool, device: str) -> float:
+# at most 64 MB of float32 per --dump-outputs directory, split over the two
+# large arrays (params, grads); the three losses are scalars
+DUMP_MAX_ELEMS = 7_000_000
+
+
+class ImpalaState:
+    """Snapshot/restore of everything a train step mutates, so the step a
+    --dump-outputs run writes out starts from a reproducible state. Two
+    things make the state after many updates differ between runs: the
+    clock-priming loop in run_timed() runs for a fixed TIME, i.e. a
+    machine-dependent number of updates, and the kernels' atomic
+    accumulation order puts last-bit noise into every gradient, which
+    training amplifies (measured: 4e-7 relative on the parameters after one
+    update, a few percent after 50)."""
+
+    def __init__(self, agent):
+        self.agent = agent
+
+    def _tensors(self):
+        opt = self.agent.optimizer
+        t = {"flat_params": opt.flat_params, "master": opt.master}
+        t.update(opt._state_tensors())
+        return t
+
+    def save(self):
+        a = self.agent
+        self._snap = {k: v.detach().clone()
+                      for k, v in self._tensors().items()}
+        self._counters = (a.optimizer.step_count, a.global_step,
+                          a.num_env_frames)
+
+    def restore(self):
+        a = self.agent
+        with torch.no_grad():
+            for k, v in self._tensors().items():
+                v.copy_(self._snap[k])
+        (a.optimizer.step_count, a.global_step,
+         a.num_env_frames) = self._counters
+
+
+def dump_outputs(out_dir: str, agent, losses) -> None:
+    """Write the last timed step's results as float32 .npy files: the three
+    losses, the updated fp32 parameters and the (gathered, pre-clip)
+    gradients. Arrays above DUMP_MAX_ELEMS are reduced to a fixed seeded
+    sample of their elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    opt = agent.optimizer
+    out = {
+        "pi_loss": losses[0], "baseline_loss": losses[1],
+        "entropy": losses[2], "params": opt.master, "grads": opt.flat_grads,
+    }
+    for name, v in out.items():
+        arr = (v.detach().float().cpu().numpy() if torch.is_tensor(v)
+               else np.asarray(v)).astype(np.float32).reshape(-1)
+        if arr.size > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng(0).choice(
+                arr.size, DUMP_MAX_ELEMS, replace=False)
+            idx.sort()
+            arr = arr[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
+def run_timed(step, args, world: int, have_gpu: bool, device: str,
+              state=None) -> float:
     """Warmup (+ untimed clock priming), then time EXACTLY args.steps steps
     bracketed by barrier+synchronize; returns MAX-over-ranks elapsed
-    seconds. ``step(i)`` must run one full train step."""
+    seconds. ``step(i)`` must run one full train step.
+
+    ``state`` (save()/restore(), --dump-outputs runs only): the seeded
+    initial training state is saved before the first step and put back
+    right before the LAST timed step, and the batch index of the timed
+    steps is fixed, so that step computes one update from bit-identical
+    weights on the same batch in every run. The restore is three
+    stream-ordered device copies (~40 MB, tens of microseconds) inside the
+    timed region of such runs only; plain runs are untouched."""
 
     def barrier_sync():
         if world > 1:
@@ -98,6 +191,8 @@ def run_timed(step, args, world: int, have_gpu: bool, device: str) -> float:
 
     t_warm0 = time.perf_counter()
     i = 0
+    if state is not None:
+        state.save()
     for _ in range(args.warmup):
         step(i)
         i += 1
@@ -111,6 +206,12 @@ def run_timed(step, args, world: int, have_gpu: bool, device: str) -> float:
             step(i)
             i += 1
     barrier_sync()
+    if state is not None:
+        # the priming loop above advanced i by a machine-dependent count:
+        # restart the batch index where the warmup left it (the absorbing
+        # step below queues batch i for the pipelined upload, which the
+        # first timed step then consumes)
+        i = args.warmup
     if have_gpu:
         # the FIRST replay after a full device sync intermittently costs
         # ~1-2 ms extra (driver wake-up); absorb it untimed so the short
@@ -127,6 +228,8 @@ def run_timed(step, args, world: int, have_gpu: bool, device: str) -> float:
     if events:
         events[0].record()
     for k in range(args.steps):
+        if state is not None and k == args.steps - 1:
+            state.restore()  # stream-ordered before the step below
         step(i)
         i += 1
         if events:
@@ -222,17 +325,25 @@ def bench_impala(args, rank, world, local_rank, have_gpu, device):
                     graphed.pinned[k].dtype).pin_memory()
                 for k, v in b.items()})
 
+    last = [None]  # what the most recent step returned to its caller
+
     def step(i: int):
         if graphed is not None:
-            return graphed.step(pinned_src=pinned_pool[i % len(pinned_pool)])
+            last[0] = graphed.step(
+                pinned_src=pinned_pool[i % len(pinned_pool)])
+            return last[0]
         b = pool[i % len(pool)]
-        return agent.train(
+        last[0] = agent.train(
             state=b["state"], reward=b["reward"], action=b["action"],
             done=b["done"], behavior_policy=b["behavior_policy"],
             previous_action=b["previous_action"], initial_h=b["initial_h"],
             initial_c=b["initial_c"])
+        return last[0]
 
-    dt = run_timed(step, args, world, have_gpu, device)
+    dt = run_timed(step, args, world, have_gpu, device,
+                   state=ImpalaState(agent) if args.dump_outputs else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, agent, last[0])
     frames = args.steps * B * T * world
     emit(rank,
          "learner env-frames/sec (whole node), IMPALA deep-conv 84x84x4",

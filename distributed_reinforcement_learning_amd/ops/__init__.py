@@ -17,10 +17,23 @@ import os
 _EXT = None
 _IMPORT_ERROR: Exception | None = None
 
-try:
-    from distributed_reinforcement_learning_amd.ops import _drla_hip as _EXT  # type: ignore
-except ImportError as e:  # extension not built (CPU-only dev) — fallbacks run
-    _IMPORT_ERROR = e
+def _load() -> bool:
+    """(Re)try the extension import. Called at package import, and again by
+    the in-tree build once it has written the .so: on a fresh checkout this
+    package is imported (to reach ops.build) before the extension exists."""
+    global _EXT, _IMPORT_ERROR
+    if _EXT is None:
+        try:
+            import importlib
+            importlib.invalidate_caches()  # the .so may be newer than the dir cache
+            from distributed_reinforcement_learning_amd.ops import _drla_hip  # type: ignore
+            _EXT, _IMPORT_ERROR = _drla_hip, None
+        except ImportError as e:  # not built (CPU-only dev) — fallbacks run
+            _IMPORT_ERROR = e
+    return _EXT is not None
+
+
+_load()
 
 
 def available() -> bool:

@@ -90,6 +90,10 @@ def build(verbose: bool = True, force: bool = False) -> str:
         check=True, cwd=repo_root)
     if verbose:
         print(f"[drla build] wrote {OUT_SO} (import check OK)")
+    # this process imported the ops package (to get here) before the .so
+    # existed on a fresh checkout: pick the extension up now
+    from distributed_reinforcement_learning_amd import ops
+    ops._load()
     return OUT_SO
 
 

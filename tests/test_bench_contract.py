@@ -6,9 +6,24 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cpu_env():
+    """Environment that hides every GPU from the child processes: these
+    launches test the CPU/gloo path, also on a machine that has GPUs (and
+    fewer of them than ranks). torch on ROCm honours HIP_VISIBLE_DEVICES,
+    CUDA_VISIBLE_DEVICES alone does not hide the devices there; an invalid
+    ordinal ends the visible-device list."""
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="-1",
+               HIP_VISIBLE_DEVICES="-1")
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    return env
+
 
 BENCH_ARGS = ["--steps", "2", "--warmup", "1", "--batch", "2",
               "--trajectory", "4", "--lstm", "16", "--pool", "2"]
@@ -36,6 +51,63 @@ def test_bench_single_process():
     _check_line(r.stdout.strip().splitlines()[-1], 1)
 
 
+def _dump_twice(tmp_path, env=None):
+    """Two bench runs with the same arguments (the second with --full),
+    each dumping its outputs; returns the two {file: array} dicts."""
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, "bench.py"] + BENCH_ARGS + extra
+            + ["--dump-outputs", str(d)],
+            capture_output=True, text=True, cwd=REPO, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        _check_line(r.stdout.strip().splitlines()[-1], 1)
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["baseline_loss.npy", "entropy.npy", "grads.npy",
+                         "params.npy", "pi_loss.npy"]
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert all(np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+        assert arrs["params.npy"].size > 1000
+        assert np.abs(arrs["grads.npy"]).max() > 0
+        dumps.append(arrs)
+    return dumps
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32 .npy
+    (<= 64 MB in all), bit-identical on the CPU path for two runs with the
+    same arguments; --full is accepted and leaves the result line alone."""
+    a, b = _dump_twice(tmp_path, _cpu_env())
+    for f in a:
+        np.testing.assert_array_equal(a[f], b[f])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_reproducible_gpu(tmp_path):
+    """Same on the graphed GPU path. The dumped step runs from the
+    restored, bit-identical initial weights on a fixed batch, so neither the
+    machine-dependent number of clock-priming updates nor noise amplified by
+    earlier updates may show; what is left is one step's atomic
+    accumulation-order noise: a gradient element may flip by one bf16 ulp
+    (2^-8 relative, bounded here against the array's largest magnitude),
+    and one RMSProp update moves a parameter by at most
+    lr/sqrt(1-rho) = 6e-4/0.1, of which a 1-ulp gradient flip perturbs
+    2^-7 relative. The losses come from bf16 logits/values, so they are
+    held to one bf16 ulp."""
+    a, b = _dump_twice(tmp_path)
+    g_tol = 2.0 ** -8 * np.abs(a["grads.npy"]).max()
+    p_tol = (6e-4 / 0.1) * 2.0 ** -7
+    np.testing.assert_allclose(a["grads.npy"], b["grads.npy"],
+                               rtol=0, atol=g_tol)
+    np.testing.assert_allclose(a["params.npy"], b["params.npy"],
+                               rtol=0, atol=p_tol)
+    for f in ("pi_loss.npy", "baseline_loss.npy", "entropy.npy"):
+        np.testing.assert_allclose(a[f], b[f], rtol=2.0 ** -8)
+
+
 @pytest.mark.parametrize("algo,extra", [
     ("apex", ["--batch", "4"]),
     ("r2d2", ["--batch", "2", "--seq-len", "6", "--burn-in", "2"]),
@@ -60,9 +132,7 @@ def test_bench_algo_flags(algo, extra):
 
 def test_bench_torchrun_two_ranks():
     """Exactly the driver's multi-GPU launch shape, on CPU/gloo."""
-    env = dict(os.environ)
-    env.pop("WORLD_SIZE", None)
-    env.pop("RANK", None)
+    env = _cpu_env()
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -81,9 +151,7 @@ def test_bench_torchrun_four_ranks():
     """The driver's N=4 launch shape (gloo on CPU): rank logic, pool
     seeding, MAX-over-ranks timing and the single rank-0 JSON line must
     hold beyond 2 ranks."""
-    env = dict(os.environ)
-    env.pop("WORLD_SIZE", None)
-    env.pop("RANK", None)
+    env = _cpu_env()
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "4", "--master-addr", "127.0.0.1",

@@ -34,7 +34,11 @@ def test_impala_two_rank_learner_spawn(tmp_path):
     for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(var, None)
     env["MASTER_ADDR"] = "127.0.0.1"
-    env["CUDA_VISIBLE_DEVICES"] = ""  # force the gloo/CPU path
+    # force the gloo/CPU path: torch on ROCm honours HIP_VISIBLE_DEVICES
+    # (CUDA_VISIBLE_DEVICES alone does not hide the devices there); an
+    # invalid ordinal ends the visible-device list
+    env["CUDA_VISIBLE_DEVICES"] = "-1"
+    env["HIP_VISIBLE_DEVICES"] = "-1"
     run = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",

@@ -7,6 +7,7 @@ release/acquire — and runs it under TSan. A race report or a
 checksum/torn-snapshot violation fails the test.
 """
 
+import ctypes
 import shutil
 import subprocess
 import sys
@@ -26,6 +27,13 @@ def _tsan_available() -> bool:
     return probe.returncode == 0
 
 
+def _no_aslr():
+    """personality(ADDR_NO_RANDOMIZE) for the child only: older TSan
+    runtimes abort with "unexpected memory mapping" on kernels with high
+    mmap randomization entropy instead of re-executing themselves."""
+    ctypes.CDLL(None).personality(0x0040000)
+
+
 @pytest.mark.skipif(not _tsan_available(),
                     reason="g++ -fsanitize=thread unavailable")
 def test_ring_and_seqlock_tsan_clean(tmp_path):
@@ -37,7 +45,8 @@ def test_ring_and_seqlock_tsan_clean(tmp_path):
     assert build.returncode == 0, build.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True,
                          env={"TSAN_OPTIONS": "halt_on_error=1",
-                              "PATH": "/usr/bin:/bin"}, timeout=120)
+                              "PATH": "/usr/bin:/bin"}, timeout=120,
+                         preexec_fn=_no_aslr)
     sys.stderr.write(run.stderr)
     assert run.returncode == 0, (run.stdout, run.stderr)
     assert "OK" in run.stdout
