@@ -39,19 +39,34 @@ SOURCES = [
 ]
 
 
-def _existing_sources() -> List[str]:
-    return [os.path.join(HIP_DIR, s) for s in SOURCES
-            if os.path.exists(os.path.join(HIP_DIR, s))]
+def source_paths() -> List[str]:
+    """The translation units handed to hipcc; a listed file that is missing
+    is an error here, not an undefined symbol at import time."""
+    paths = [os.path.join(HIP_DIR, s) for s in SOURCES]
+    missing = [p for p in paths if not os.path.isfile(p)]
+    if missing:
+        raise FileNotFoundError(
+            "listed in SOURCES but not on disk: " + ", ".join(missing))
+    return paths
+
+
+def dependency_paths() -> List[str]:
+    """Every file that goes into the .so: SOURCES plus the headers in hip/
+    (kernel signatures and shared shape constants live there, so a header
+    edit must rebuild)."""
+    headers = sorted(os.path.join(HIP_DIR, f) for f in os.listdir(HIP_DIR)
+                     if f.endswith(".h"))
+    return source_paths() + headers
 
 
 def build(verbose: bool = True, force: bool = False) -> str:
     import torch
 
     torch_dir = os.path.dirname(os.path.abspath(torch.__file__))
-    sources = _existing_sources()
+    sources = source_paths()
     if not force and os.path.exists(OUT_SO):
         so_mtime = os.path.getmtime(OUT_SO)
-        if all(os.path.getmtime(s) < so_mtime for s in sources):
+        if all(os.path.getmtime(d) < so_mtime for d in dependency_paths()):
             if verbose:
                 print(f"[drla build] {OUT_SO} up to date")
             return OUT_SO

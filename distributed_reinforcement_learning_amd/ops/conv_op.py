@@ -1,7 +1,8 @@
 """Custom MFMA conv stack autograd wrapper (K1, ops/hip/conv.hip).
 
-Layer ids (conv.hip convcfg): 0 = 84x84x4 u8 -> 20x20x32 (IMPALA/A3C/Ape-X),
-1 = 84x84x1 u8 (R2D2 POMDP), 2 = 20x20x32 -> 9x9x64, 3 = 9x9x64 -> 7x7x64.
+Layer ids (DRLA_CONV_LAYERS in hip/drla_common.h): 0 = 84x84x4 u8 ->
+20x20x32 (IMPALA/A3C/Ape-X), 1 = 84x84x1 u8 (R2D2 POMDP), 2 = 20x20x32 ->
+9x9x64, 3 = 9x9x64 -> 7x7x64.
 
 The forward fuses /255-normalize (u8 layers), bias and ReLU; the backward is
 relu-mask -> custom wgrad (MFMA, split-M atomics) + dgrad (MFMA implicit

@@ -16,11 +16,9 @@
 //   dlogits_n = [gpi * -adv*w*(onehot - p) + ge * p*(log p - E)] / N
 //   dV_n      = gb * (-2 adv) / N
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
-typedef unsigned short a2c_bf16;
-
-__device__ __forceinline__ float a2c_ld(const a2c_bf16* p16,
+__device__ __forceinline__ float a2c_ld(const bf16raw* p16,
                                         const float* p32, long long i) {
   if (p16) {
     unsigned int x = ((unsigned int)p16[i]) << 16;
@@ -39,7 +37,7 @@ __device__ __forceinline__ float a2c_clip(float r, int mode) {
 }
 
 extern "C" __global__ void drla_a2c_loss_fwd(
-    const a2c_bf16* __restrict__ lg16, const float* __restrict__ lg32,
+    const bf16raw* __restrict__ lg16, const float* __restrict__ lg32,
     const float* __restrict__ value,       // [N]
     const float* __restrict__ next_value,  // [N]
     const int* __restrict__ actions,       // [N]
@@ -87,7 +85,7 @@ extern "C" __global__ void drla_a2c_loss_bwd(
     const float* __restrict__ p_stash, const float* __restrict__ adv_st,
     const int* __restrict__ actions, const float* __restrict__ grad3,
     int from_total, float c_bl, float c_ent,
-    a2c_bf16* __restrict__ dlg16, float* __restrict__ dlg32,
+    bf16raw* __restrict__ dlg16, float* __restrict__ dlg32,
     float* __restrict__ dvalue, int N, int A) {
   const float gpi = grad3[0];
   const float gb = from_total ? gpi * c_bl : grad3[1];

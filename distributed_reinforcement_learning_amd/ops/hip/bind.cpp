@@ -1,220 +1,19 @@
 // PyTorch bindings for the drla gfx950 kernels (native HIP — no CUDA
 // masquerade: ATen/hip API, hipLaunchKernelGGL on the current HIP stream).
 // Compiled by hipcc together with the .hip translation units (see
-// build_ext.py); loaded as distributed_reinforcement_learning_amd.ops._drla_hip.
+// ops/build.py); loaded as
+// distributed_reinforcement_learning_amd.ops._drla_hip.
+// Kernel signatures and every shape constant shared with the kernels come
+// from drla_kernels.h / drla_common.h — none is restated here.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <tuple>
 
-#include "drla_common.h"
-
-// kernel decls (defined in the .hip TUs)
-extern "C" __global__ void drla_u8_normalize_f32(const uchar4*, float4*,
-                                                 long long);
-typedef __attribute__((ext_vector_type(4))) unsigned short ushort4v;
-extern "C" __global__ void drla_u8_normalize_bf16(const uchar4*, ushort4v*,
-                                                  long long);
-extern "C" __global__ void drla_u8_normalize_f32_tail(const unsigned char*,
-                                                      float*, long long,
-                                                      long long);
-extern "C" __global__ void drla_u8_normalize_bf16_tail(const unsigned char*,
-                                                       unsigned short*,
-                                                       long long, long long);
-// conv stack (conv.hip)
-extern "C" __global__ void drla_mfma_probe(const unsigned short*,
-                                           const unsigned short*, float*);
-extern "C" __global__ void drla_conv_fwd_l1(const unsigned char*,
-                                            const unsigned short*,
-                                            const unsigned short*,
-                                            unsigned short*, int,
-                                            unsigned char*);
-extern "C" __global__ void drla_conv_fwd_l1_c1(const unsigned char*,
-                                               const unsigned short*,
-                                               const unsigned short*,
-                                               unsigned short*, int,
-                                               unsigned char*);
-extern "C" __global__ void drla_conv_fwd_l2(const unsigned short*,
-                                            const unsigned short*,
-                                            const unsigned short*,
-                                            unsigned short*, int);
-extern "C" __global__ void drla_conv_fwd_l3(const unsigned short*,
-                                            const unsigned short*,
-                                            const unsigned short*,
-                                            unsigned short*, int);
-extern "C" __global__ void drla_relu_mask_bwd(const unsigned short*,
-                                              const unsigned short*,
-                                              unsigned short*, float*,
-                                              long long, int, long long,
-                                              long long);
-extern "C" __global__ void drla_wgrad_finalize(float*, unsigned short*,
-                                               int, int, float*,
-                                               unsigned short*);
-extern "C" __global__ void drla_conv_wgrad_l1(const unsigned char*,
-                                              const unsigned short*, float*,
-                                              int);
-extern "C" __global__ void drla_conv_wgrad_l1_c1(const unsigned char*,
-                                                 const unsigned short*,
-                                                 float*, int);
-extern "C" __global__ void drla_conv_wgrad_l2(const unsigned short*,
-                                              const unsigned short*, float*,
-                                              int);
-extern "C" __global__ void drla_conv_wgrad_l3(const unsigned short*,
-                                              const unsigned short*, float*,
-                                              int);
-extern "C" __global__ void drla_conv_dgrad_l2(const unsigned short*,
-                                              const unsigned short*,
-                                              unsigned short*, int);
-extern "C" __global__ void drla_conv_dgrad_l3(const unsigned short*,
-                                              const unsigned short*,
-                                              unsigned short*, int);
-extern "C" __global__ void drla_dqn_loss_fwd(
-    const unsigned short*, const float*, const float*, const float*,
-    const int*, const float*, const float*, const float*, float*, float*,
-    int, int);
-extern "C" __global__ void drla_dqn_loss_bwd(
-    const float*, const int*, const float*, const float*, unsigned short*,
-    float*, int, int);
-extern "C" __global__ void drla_a2c_loss_fwd(
-    const unsigned short*, const float*, const float*, const float*,
-    const int*, const float*, const unsigned char*, float, int, float,
-    float, float*, float*, float*, int, int);
-extern "C" __global__ void drla_a2c_loss_bwd(
-    const float*, const float*, const int*, const float*, int, float,
-    float, unsigned short*, float*, float*, int, int);
-extern "C" __global__ void drla_r2d2_loss_fwd(
-    const unsigned short*, const float*, const unsigned short*,
-    const float*, const int*, const float*, const unsigned char*,
-    const float*, float, int, float*, float*, float*, int, int, int);
-extern "C" __global__ void drla_dueling_head_fwd(
-    const float*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, unsigned short*, int,
-    int, int, int, int, int);
-extern "C" __global__ void drla_dhead_train_fwd(
-    const float*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, unsigned short*,
-    unsigned short*, int, int, int, int);
-extern "C" __global__ void drla_dhead_train_bwd(
-    const unsigned short*, const unsigned short*, const float*,
-    const unsigned short*, const unsigned short*, float*, float*, int,
-    int, int, int);
-extern "C" __global__ void drla_dhead_train_fin(
-    const float*, unsigned short*, unsigned short*, unsigned short*,
-    unsigned short*, int, int, int);
-extern "C" __global__ void drla_r2d2_loss_bwd(
-    const float*, const int*, const float*, const float*, unsigned short*,
-    float*, int, int, int);
-extern "C" __global__ void drla_per_update(float*, const long long*,
-                                           const float*, int, long long);
-extern "C" __global__ void drla_per_sample(const float*, const float*,
-                                           const float*, long long*,
-                                           float*, int, long long);
-extern "C" __global__ void drla_per_rebuild_level(float*, long long,
-                                                  long long);
-extern "C" __global__ void drla_multi_gather(
-    const long long*, const unsigned long long*, const unsigned long long*,
-    const long long*, int);
-extern "C" __global__ void drla_embed_bwd_scatter(
-    const long long*, const unsigned short*, const float*, float*,
-    long long, int, long long);
-extern "C" __global__ void drla_f32_to_bf16_zero_kernel(float*,
-                                                        unsigned short*,
-                                                        long long);
-
-extern "C" __global__ void drla_vtrace_scan(const float*, const float*,
-                                            const float*, float*, int, int);
-extern "C" __global__ void drla_vtrace_loss_fwd(
-    const unsigned short*, const float*, const float*, const float*,
-    const int*, const float*, const unsigned char*, float, int, float,
-    float, float*, float*, float*, float*, int, int, int);
-extern "C" __global__ void drla_vtrace_loss_bwd(
-    const float*, const float*, const float*, const float*, const int*,
-    const float*, int, float, float, unsigned short*, float*, float*, int,
-    int, int);
-extern "C" __global__ void drla_lstm_tail_fwd(const float*, const float*,
-                                              float*, float*, float*, float,
-                                              long long, int);
-extern "C" __global__ void drla_lstm_tail_bwd(const float*, const float*,
-                                              const float*, const float*,
-                                              const float*, float*, float*,
-                                              long long, int, long long);
-extern "C" __global__ void drla_lstm_tail_fwd_bf16(
-    const unsigned short*, const float*, float*, float*, float*, float,
-    long long, int);
-extern "C" __global__ void drla_lstm_tail_bwd_bf16(
-    const float*, const float*, const float*, const float*, const float*,
-    unsigned short*, float*, long long, int, long long);
-extern "C" __global__ void drla_mlp_heads_fwd(
-    const float*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    const unsigned short*, unsigned short*, float*, unsigned short*, int,
-    int);
-extern "C" __global__ void drla_mlp_heads_bwd(
-    const unsigned short*, const float*, const unsigned short*,
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    unsigned short*, unsigned short*, unsigned short*, unsigned short*,
-    float*, float*, float*, float*, float*, float*, float*, int, int);
-extern "C" __global__ void drla_heads_wt_pack(
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    unsigned short*, int);
-extern "C" __global__ void drla_heads_wgrad(
-    const unsigned short*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, const float*,
-    const unsigned short*, unsigned short*, unsigned short*, unsigned short*,
-    unsigned short*, unsigned short*, unsigned short*, const float*,
-    unsigned short*, unsigned short*, unsigned short*, unsigned short*,
-    unsigned short*, unsigned short*, int, int);
-extern "C" __global__ void drla_embed_mlp_fwd(
-    const long long*, const unsigned short*, const unsigned short*,
-    const unsigned short*, const unsigned short*, unsigned short*,
-    unsigned short*, int, int);
-extern "C" __global__ void drla_embed_w2t_pack(const unsigned short*,
-                                               unsigned short*);
-extern "C" __global__ void drla_embed_mlp_bwd(
-    const unsigned short*, long long, const unsigned short*,
-    const unsigned short*, const unsigned short*, unsigned short*,
-    unsigned short*, float*, int);
-extern "C" __global__ void drla_embed_finalize(float*, unsigned short*,
-                                               unsigned short*,
-                                               unsigned short*, long long);
-extern "C" __global__ void drla_grad_gather(
-    const unsigned long long*, const long long*, const long long*,
-    unsigned short*, int, long long, float*, int);
-extern "C" __global__ void drla_lstm_seq_train_fwd(
-    const unsigned short*, const unsigned short*, const float*, const float*,
-    const unsigned char*, float*, float*, float*, float*, float*,
-    unsigned short*, float, int, int, int);
-extern "C" __global__ void drla_lstm_seq_train_bwd(
-    const float*, const float*, const float*, const float*, const float*,
-    const unsigned short*, const unsigned char*, unsigned short*, float*,
-    float*, int, int, int);
-extern "C" __global__ void drla_lstm_seq_fwd(
-    const unsigned short*, const float*, const unsigned short*, const float*,
-    const float*, const unsigned char*, float*, float*, float*, float, int,
-    int, int);
-extern "C" __global__ void drla_sq_norm(const float*, float*, long long);
-extern "C" __global__ void drla_sq_norm_bf16(const unsigned short*, float*,
-                                             long long);
-extern "C" __global__ void drla_rmsprop_step_bf16(
-    unsigned short*, const unsigned short*, float*, float*, const float*,
-    float, const float*, float, float, long long);
-extern "C" __global__ void drla_adam_step_bf16(
-    unsigned short*, const unsigned short*, float*, float*, float*,
-    const float*, float, const float*, float, float, float, long long);
-extern "C" __global__ void drla_rmsprop_step(float*, const float*, float*,
-                                             const float*, float,
-                                             const float*, float, float,
-                                             long long);
-extern "C" __global__ void drla_adam_step(float*, const float*, float*,
-                                          float*, const float*, float,
-                                          const float*, float, float, float,
-                                          long long);
+#include "drla_kernels.h"
 
 namespace {
 
@@ -222,10 +21,46 @@ hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
 
+// ---- argument checks and typed pointers -----------------------------------
 void check_gpu_contig(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
+
+template <typename... Ts>
+void check_all_gpu_contig(const char* what, const Ts&... ts) {
+  (check_gpu_contig(ts, what), ...);
+}
+
+// bf16 bits of a tensor that must BE bf16 (data_ptr<float>() checks its
+// dtype; a bare reinterpret would not). BF16P / BF16PM name the argument.
+bf16raw* bf16_ptr(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
+  return static_cast<bf16raw*>(t.data_ptr());
+}
+#define BF16P(t) static_cast<const bf16raw*>(bf16_ptr(t, #t))
+#define BF16PM(t) bf16_ptr(t, #t)
+
+// kernels that take bf16 OR float32 have a pointer pair, one of them null
+struct DualPtr { bf16raw* bf16; float* f32; };
+DualPtr dual_ptr(const torch::Tensor& t) {
+  if (t.scalar_type() == torch::kBFloat16)
+    return {static_cast<bf16raw*>(t.data_ptr()), nullptr};
+  return {nullptr, t.data_ptr<float>()};
+}
+
+const unsigned char* boolp(const torch::Tensor& t) {
+  return reinterpret_cast<const unsigned char*>(t.data_ptr<bool>());
+}
+// int64 tables: indices (i64p) or raw device addresses (u64p)
+long long* i64p(const torch::Tensor& t) {
+  return reinterpret_cast<long long*>(t.data_ptr<int64_t>());
+}
+const unsigned long long* u64p(const torch::Tensor& t) {
+  return reinterpret_cast<const unsigned long long*>(t.data_ptr<int64_t>());
+}
+
+// ---- frame normalize, V-trace scan ----------------------------------------
 
 torch::Tensor normalize_frames_f32(torch::Tensor frames) {
   check_gpu_contig(frames, "frames");
@@ -263,8 +98,7 @@ torch::Tensor normalize_frames_bf16(torch::Tensor frames) {
   if (n % 4) {
     hipLaunchKernelGGL(drla_u8_normalize_bf16_tail, dim3(1), dim3(DRLA_BLOCK),
                        0, cur_stream(), frames.data_ptr<uint8_t>(),
-                       reinterpret_cast<unsigned short*>(out.data_ptr()),
-                       n4 * 4, n);
+                       BF16PM(out), n4 * 4, n);
   }
   return out;
 }
@@ -286,29 +120,31 @@ torch::Tensor vtrace_scan(torch::Tensor deltas, torch::Tensor discounts,
 }
 
 // ---- conv stack ----------------------------------------------------------
-namespace convcfg {
-struct Layer { int ci, co, kh, kw, stride, hi, wi, ho, wo; };
-static const Layer L[4] = {
-    {4, 32, 8, 8, 4, 84, 84, 20, 20},   // 0: l1 (u8 x4)
-    {1, 32, 8, 8, 4, 84, 84, 20, 20},   // 1: l1_c1 (u8 x1)
-    {32, 64, 4, 4, 2, 20, 20, 9, 9},    // 2: l2
-    {64, 64, 3, 3, 1, 9, 9, 7, 7},      // 3: l3
-};
-}  // namespace convcfg
+// kernel per layer, indexed like DRLA_CONV_LAYERS; the two u8 layers share
+// one signature, the two bf16 layers the other
+constexpr auto kConvFwdU8 = std::array{&drla_conv_fwd_l1, &drla_conv_fwd_l1_c1};
+constexpr auto kConvFwdBf16 = std::array{&drla_conv_fwd_l2, &drla_conv_fwd_l3};
+constexpr auto kConvWgradU8 =
+    std::array{&drla_conv_wgrad_l1, &drla_conv_wgrad_l1_c1};
+constexpr auto kConvWgradBf16 =
+    std::array{&drla_conv_wgrad_l2, &drla_conv_wgrad_l3};
 
-static const unsigned short* u16p(const torch::Tensor& t) {
-  return reinterpret_cast<const unsigned short*>(t.data_ptr());
+const DrlaConvLayer& conv_layer(int layer) {
+  TORCH_CHECK(layer >= 0 && layer < 4, "bad layer");
+  return DRLA_CONV_LAYERS[layer];
 }
-static unsigned short* u16pm(torch::Tensor& t) {
-  return reinterpret_cast<unsigned short*>(t.data_ptr());
-}
+int conv_m_tiles(int rows) { return (rows + DRLA_CONV_BM - 1) / DRLA_CONV_BM; }
 
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
   check_gpu_contig(A, "A");
   check_gpu_contig(B, "B");
   auto D = torch::empty({16, 16}, A.options().dtype(torch::kFloat));
+  // unchecked on purpose: the probe takes raw 16-bit patterns, and its test
+  // passes them as uint16 views
   hipLaunchKernelGGL(drla_mfma_probe, dim3(1), dim3(64), 0, cur_stream(),
-                     u16p(A), u16p(B), D.data_ptr<float>());
+                     static_cast<const bf16raw*>(A.data_ptr()),
+                     static_cast<const bf16raw*>(B.data_ptr()),
+                     D.data_ptr<float>());
   return D;
 }
 
@@ -318,15 +154,11 @@ std::tuple<torch::Tensor, torch::Tensor> conv_fwd(
   check_gpu_contig(in, "in");
   check_gpu_contig(w, "w");
   check_gpu_contig(bias, "bias");
-  const auto& cfg = convcfg::L[layer];
-  TORCH_CHECK(w.scalar_type() == torch::kBFloat16, "weights must be bf16");
-  TORCH_CHECK(bias.scalar_type() == torch::kBFloat16, "bias must be bf16");
+  const auto& cfg = conv_layer(layer);
   const int batch = in.size(0);
-  const int M = batch * cfg.ho * cfg.wo;
   auto out = torch::empty({batch, cfg.ho, cfg.wo, cfg.co},
                           in.options().dtype(torch::kBFloat16));
-  const int grid = (M + 127) / 128;
-  auto* outp = u16pm(out);
+  const dim3 grid(conv_m_tiles(batch * cfg.ho * cfg.wo));
   // stashed-input mode (u8 layers only): the kernel bundles a
   // pass-through copy of the input so the backward never re-reads the
   // (possibly upload-overlapped) source buffer
@@ -338,36 +170,22 @@ std::tuple<torch::Tensor, torch::Tensor> conv_fwd(
     x_stash = torch::empty_like(in);
     stashp = x_stash.data_ptr<uint8_t>();
   }
-  switch (layer) {
-    case 0:
-      hipLaunchKernelGGL(drla_conv_fwd_l1, dim3(grid), dim3(256), 0,
-                         cur_stream(), in.data_ptr<uint8_t>(), u16p(w),
-                         u16p(bias), outp, batch, stashp);
-      break;
-    case 1:
-      hipLaunchKernelGGL(drla_conv_fwd_l1_c1, dim3(grid), dim3(256), 0,
-                         cur_stream(), in.data_ptr<uint8_t>(), u16p(w),
-                         u16p(bias), outp, batch, stashp);
-      break;
-    case 2:
-      hipLaunchKernelGGL(drla_conv_fwd_l2, dim3(grid), dim3(256), 0,
-                         cur_stream(), u16p(in), u16p(w),
-                         u16p(bias), outp, batch);
-      break;
-    case 3:
-      hipLaunchKernelGGL(drla_conv_fwd_l3, dim3(grid), dim3(256), 0,
-                         cur_stream(), u16p(in), u16p(w),
-                         u16p(bias), outp, batch);
-      break;
-    default:
-      TORCH_CHECK(false, "bad layer");
+  if (layer <= 1) {
+    hipLaunchKernelGGL(kConvFwdU8[layer], grid, dim3(DRLA_CONV_BLOCK), 0,
+                       cur_stream(), in.data_ptr<uint8_t>(), BF16P(w),
+                       BF16P(bias), BF16PM(out), batch, stashp);
+  } else {
+    hipLaunchKernelGGL(kConvFwdBf16[layer - 2], grid, dim3(DRLA_CONV_BLOCK),
+                       0, cur_stream(), BF16P(in), BF16P(w), BF16P(bias),
+                       BF16PM(out), batch);
   }
   return {out, x_stash};
 }
 
-// persistent [16][64] bias-grad partial slots shared by relu_mask_bwd
-// (atomic producers, compute stream) and wgrad_finalize (sum + re-zero
-// consumer — which may run on the SIDE wgrad stream, see ops/conv_op.py),
+// persistent [DRLA_DBIAS_SLOTS][DRLA_DBIAS_STRIDE] bias-grad partial slots
+// shared by relu_mask_bwd (atomic producers, compute stream) and
+// wgrad_finalize (sum + re-zero consumer — which may run on the SIDE
+// wgrad stream, see ops/conv_op.py),
 // so each conv layer owns its own slot set: a later layer's mask must not
 // touch slots a pending finalize still reads.
 static torch::Tensor& dbias_slot_buf(const torch::Tensor& like,
@@ -376,7 +194,8 @@ static torch::Tensor& dbias_slot_buf(const torch::Tensor& like,
   TORCH_CHECK(slot_id >= 0 && slot_id < 4, "bad slot id");
   if (!bufs[slot_id].defined()) {
     bufs[slot_id] =
-        torch::zeros({16 * 64}, like.options().dtype(torch::kFloat));
+        torch::zeros({DRLA_DBIAS_SLOTS * DRLA_DBIAS_STRIDE},
+                     like.options().dtype(torch::kFloat));
   }
   return bufs[slot_id];
 }
@@ -412,10 +231,9 @@ torch::Tensor relu_mask_bwd(torch::Tensor dy, torch::Tensor y, int64_t CO,
   int grid = drla_grid(n / 8);
   if (grid > 640) grid = 640;
   hipLaunchKernelGGL(drla_relu_mask_bwd, dim3(grid), dim3(DRLA_BLOCK),
-                     0, cur_stream(),
-                     reinterpret_cast<const unsigned short*>(dy.data_ptr()),
-                     u16p(y), u16pm(out), slots.data_ptr<float>(), n,
-                     (int)CO, n_stride, row_elems);
+                     0, cur_stream(), BF16P(dy), BF16P(y), BF16PM(out),
+                     slots.data_ptr<float>(), n, (int)CO, n_stride,
+                     row_elems);
   return out;
 }
 
@@ -424,7 +242,7 @@ std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
                                                     torch::Tensor dy) {
   check_gpu_contig(in, "in");
   check_gpu_contig(dy, "dy");
-  const auto& cfg = convcfg::L[layer];
+  const auto& cfg = conv_layer(layer);
   const int batch = in.size(0);
   const int K = cfg.kh * cfg.kw * cfg.ci;
   // runtime-tunable M-split (DRLA_WGRAD_SPLIT sweeps it; defaults from the
@@ -441,30 +259,15 @@ std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
         torch::zeros({K, cfg.co}, dy.options().dtype(torch::kFloat));
   }
   auto scratch = scratch_cache[layer];
-  dim3 grid((K + 63) / 64, split);
-  switch (layer) {
-    case 0:
-      hipLaunchKernelGGL(drla_conv_wgrad_l1, grid, dim3(256), 0,
-                         cur_stream(), in.data_ptr<uint8_t>(), u16p(dy),
-                         scratch.data_ptr<float>(), batch);
-      break;
-    case 1:
-      hipLaunchKernelGGL(drla_conv_wgrad_l1_c1, grid, dim3(256), 0,
-                         cur_stream(), in.data_ptr<uint8_t>(), u16p(dy),
-                         scratch.data_ptr<float>(), batch);
-      break;
-    case 2:
-      hipLaunchKernelGGL(drla_conv_wgrad_l2, grid, dim3(256), 0,
-                         cur_stream(), u16p(in), u16p(dy),
-                         scratch.data_ptr<float>(), batch);
-      break;
-    case 3:
-      hipLaunchKernelGGL(drla_conv_wgrad_l3, grid, dim3(256), 0,
-                         cur_stream(), u16p(in), u16p(dy),
-                         scratch.data_ptr<float>(), batch);
-      break;
-    default:
-      TORCH_CHECK(false, "bad layer");
+  const dim3 grid((K + DRLA_CONV_WGRAD_BK - 1) / DRLA_CONV_WGRAD_BK, split);
+  if (layer <= 1) {
+    hipLaunchKernelGGL(kConvWgradU8[layer], grid, dim3(DRLA_CONV_BLOCK), 0,
+                       cur_stream(), in.data_ptr<uint8_t>(), BF16P(dy),
+                       scratch.data_ptr<float>(), batch);
+  } else {
+    hipLaunchKernelGGL(kConvWgradBf16[layer - 2], grid,
+                       dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(in),
+                       BF16P(dy), scratch.data_ptr<float>(), batch);
   }
   auto dw = torch::empty({cfg.co, K}, dy.options().dtype(torch::kBFloat16));
   auto dbias = torch::empty({cfg.co}, dy.options().dtype(torch::kBFloat16));
@@ -472,8 +275,8 @@ std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
   hipLaunchKernelGGL(drla_wgrad_finalize,
                      dim3(drla_grid((long long)K * cfg.co)),
                      dim3(DRLA_BLOCK), 0, cur_stream(),
-                     scratch.data_ptr<float>(), u16pm(dw), K, cfg.co,
-                     slots.data_ptr<float>(), u16pm(dbias));
+                     scratch.data_ptr<float>(), BF16PM(dw), K, cfg.co,
+                     slots.data_ptr<float>(), BF16PM(dbias));
   return {dw, dbias};
 }
 
@@ -481,21 +284,22 @@ torch::Tensor conv_dgrad(int layer, torch::Tensor dy, torch::Tensor w) {
   check_gpu_contig(dy, "dy");
   check_gpu_contig(w, "w");
   TORCH_CHECK(layer == 2 || layer == 3, "dgrad only for l2/l3");
-  const auto& cfg = convcfg::L[layer];
+  const auto& cfg = conv_layer(layer);
   const int batch = dy.size(0);
-  const int M2 = batch * cfg.hi * cfg.wi;
   auto dx = torch::empty({batch, cfg.hi, cfg.wi, cfg.ci},
                          dy.options().dtype(torch::kBFloat16));
-  const int grid = (M2 + 127) / 128;
   if (layer == 2) {
     // parity-class kernel: blockIdx.y = (hi%2, wi%2) class, each class
     // covers batch * (hi/2) * (wi/2) rows
-    const int grid_c = (batch * (cfg.hi / 2) * (cfg.wi / 2) + 127) / 128;
-    hipLaunchKernelGGL(drla_conv_dgrad_l2, dim3(grid_c, 4), dim3(256), 0,
-                       cur_stream(), u16p(dy), u16p(w), u16pm(dx), batch);
+    const int grid_c = conv_m_tiles(batch * (cfg.hi / 2) * (cfg.wi / 2));
+    hipLaunchKernelGGL(drla_conv_dgrad_l2, dim3(grid_c, 4),
+                       dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(dy),
+                       BF16P(w), BF16PM(dx), batch);
   } else {
-    hipLaunchKernelGGL(drla_conv_dgrad_l3, dim3(grid), dim3(256), 0,
-                       cur_stream(), u16p(dy), u16p(w), u16pm(dx), batch);
+    hipLaunchKernelGGL(drla_conv_dgrad_l3,
+                       dim3(conv_m_tiles(batch * cfg.hi * cfg.wi)),
+                       dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(dy),
+                       BF16P(w), BF16PM(dx), batch);
   }
   return dx;
 }
@@ -504,20 +308,17 @@ std::tuple<torch::Tensor, torch::Tensor> dqn_loss_fwd(
     torch::Tensor main_q, torch::Tensor next_main, torch::Tensor next_tgt,
     torch::Tensor actions, torch::Tensor rewards, torch::Tensor discounts,
     torch::Tensor weights) {
-  for (auto* t : {&main_q, &next_main, &next_tgt, &actions, &rewards,
-                  &discounts, &weights})
-    check_gpu_contig(*t, "dqn_loss input");
+  check_all_gpu_contig("dqn_loss input", main_q, next_main, next_tgt,
+                       actions, rewards, discounts, weights);
   TORCH_CHECK(actions.scalar_type() == torch::kInt, "actions must be i32");
   const int B = main_q.size(0), A = main_q.size(1);
-  const bool bf16 = main_q.scalar_type() == torch::kBFloat16;
+  const DualPtr mq = dual_ptr(main_q);
   auto fopt = rewards.options().dtype(torch::kFloat);
   auto loss = torch::zeros({1}, fopt);
   auto td = torch::empty({B}, fopt);
   hipLaunchKernelGGL(
       drla_dqn_loss_fwd, dim3((B + 255) / 256), dim3(256), 0, cur_stream(),
-      bf16 ? u16p(main_q) : nullptr,
-      bf16 ? nullptr : main_q.data_ptr<float>(),
-      next_main.data_ptr<float>(), next_tgt.data_ptr<float>(),
+      mq.bf16, mq.f32, next_main.data_ptr<float>(), next_tgt.data_ptr<float>(),
       actions.data_ptr<int>(), rewards.data_ptr<float>(),
       discounts.data_ptr<float>(), weights.data_ptr<float>(),
       loss.data_ptr<float>(), td.data_ptr<float>(), B, A);
@@ -527,18 +328,17 @@ std::tuple<torch::Tensor, torch::Tensor> dqn_loss_fwd(
 torch::Tensor dqn_loss_bwd(torch::Tensor td, torch::Tensor actions,
                            torch::Tensor weights, torch::Tensor gloss,
                            int64_t A, bool want_bf16) {
-  for (auto* t : {&td, &actions, &weights, &gloss})
-    check_gpu_contig(*t, "dqn_loss bwd input");
+  check_all_gpu_contig("dqn_loss bwd input", td, actions, weights, gloss);
   const int B = td.numel();
   auto dmq = torch::empty(
       {B, A},
       td.options().dtype(want_bf16 ? torch::kBFloat16 : torch::kFloat));
+  const DualPtr out = dual_ptr(dmq);
   hipLaunchKernelGGL(
       drla_dqn_loss_bwd, dim3(((long long)B * A + 255) / 256), dim3(256), 0,
       cur_stream(), td.data_ptr<float>(), actions.data_ptr<int>(),
-      weights.data_ptr<float>(), gloss.data_ptr<float>(),
-      want_bf16 ? u16pm(dmq) : nullptr,
-      want_bf16 ? nullptr : dmq.data_ptr<float>(), B, (int)A);
+      weights.data_ptr<float>(), gloss.data_ptr<float>(), out.bf16, out.f32,
+      B, (int)A);
   return dmq;
 }
 
@@ -546,24 +346,22 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> a2c_loss_fwd(
     torch::Tensor logits, torch::Tensor value, torch::Tensor next_value,
     torch::Tensor actions, torch::Tensor rewards, torch::Tensor done,
     double gamma, int64_t clip_mode, double c_bl, double c_ent) {
-  for (auto* t : {&logits, &value, &next_value, &actions, &rewards, &done})
-    check_gpu_contig(*t, "a2c loss input");
+  check_all_gpu_contig("a2c loss input", logits, value, next_value, actions,
+                       rewards, done);
   TORCH_CHECK(actions.scalar_type() == torch::kInt, "actions must be i32");
   TORCH_CHECK(done.scalar_type() == torch::kBool, "done must be bool");
   const int N = logits.size(0), A = logits.size(1);
-  const bool bf16 = logits.scalar_type() == torch::kBFloat16;
+  const DualPtr lg = dual_ptr(logits);
   auto fopt = value.options().dtype(torch::kFloat);
   auto losses = torch::zeros({4}, fopt);
   auto p_stash = torch::empty({N, A}, fopt);
   auto adv_st = torch::empty({N}, fopt);
   hipLaunchKernelGGL(
       drla_a2c_loss_fwd, dim3((N + 255) / 256), dim3(256), 0, cur_stream(),
-      bf16 ? u16p(logits) : nullptr,
-      bf16 ? nullptr : logits.data_ptr<float>(), value.data_ptr<float>(),
+      lg.bf16, lg.f32, value.data_ptr<float>(),
       next_value.data_ptr<float>(), actions.data_ptr<int>(),
-      rewards.data_ptr<float>(),
-      reinterpret_cast<const unsigned char*>(done.data_ptr<bool>()),
-      static_cast<float>(gamma), static_cast<int>(clip_mode),
+      rewards.data_ptr<float>(), boolp(done), static_cast<float>(gamma),
+      static_cast<int>(clip_mode),
       static_cast<float>(c_bl), static_cast<float>(c_ent),
       losses.data_ptr<float>(), p_stash.data_ptr<float>(),
       adv_st.data_ptr<float>(), N, A);
@@ -574,20 +372,19 @@ std::tuple<torch::Tensor, torch::Tensor> a2c_loss_bwd(
     torch::Tensor p_stash, torch::Tensor adv_st, torch::Tensor actions,
     torch::Tensor grad3, bool from_total, double c_bl, double c_ent,
     bool want_bf16) {
-  for (auto* t : {&p_stash, &adv_st, &actions, &grad3})
-    check_gpu_contig(*t, "a2c bwd input");
+  check_all_gpu_contig("a2c bwd input", p_stash, adv_st, actions, grad3);
   const int N = p_stash.size(0), A = p_stash.size(1);
   auto dlg = torch::empty(
       {N, A}, p_stash.options().dtype(want_bf16 ? torch::kBFloat16
                                                 : torch::kFloat));
   auto dvalue = torch::empty({N}, p_stash.options());
+  const DualPtr out = dual_ptr(dlg);
   hipLaunchKernelGGL(
       drla_a2c_loss_bwd, dim3((N + 255) / 256), dim3(256), 0, cur_stream(),
       p_stash.data_ptr<float>(), adv_st.data_ptr<float>(),
       actions.data_ptr<int>(), grad3.data_ptr<float>(),
       from_total ? 1 : 0, static_cast<float>(c_bl),
-      static_cast<float>(c_ent), want_bf16 ? u16pm(dlg) : nullptr,
-      want_bf16 ? nullptr : dlg.data_ptr<float>(),
+      static_cast<float>(c_ent), out.bf16, out.f32,
       dvalue.data_ptr<float>(), N, A);
   return {dlg, dvalue};
 }
@@ -602,14 +399,14 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> r2d2_loss_fwd(
     torch::Tensor mq, torch::Tensor tq, torch::Tensor actions,
     torch::Tensor rewards, torch::Tensor done, torch::Tensor weights,
     double gamma, int64_t clip_mode) {
-  for (auto* t : {&mq, &tq, &actions, &rewards, &done, &weights})
-    check_gpu_contig(*t, "r2d2 loss input");
+  check_all_gpu_contig("r2d2 loss input", mq, tq, actions, rewards, done,
+                       weights);
   TORCH_CHECK(actions.scalar_type() == torch::kInt, "actions must be i32");
   TORCH_CHECK(done.scalar_type() == torch::kBool, "done must be bool");
   const int B = mq.size(0), W = mq.size(1), A = mq.size(2);
   TORCH_CHECK(W >= 2 && W <= 1024, "window out of range");
-  const bool bf16 = mq.scalar_type() == torch::kBFloat16;
   TORCH_CHECK(tq.scalar_type() == mq.scalar_type(), "mq/tq dtype mismatch");
+  const DualPtr m = dual_ptr(mq), t = dual_ptr(tq);
   auto fopt = rewards.options().dtype(torch::kFloat);
   auto loss = torch::zeros({1}, fopt);
   auto td_st = torch::empty({B, W - 1}, fopt);
@@ -617,11 +414,8 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> r2d2_loss_fwd(
   const int block = next_pow2(W - 1);
   hipLaunchKernelGGL(
       drla_r2d2_loss_fwd, dim3(B), dim3(block), 0, cur_stream(),
-      bf16 ? u16p(mq) : nullptr, bf16 ? nullptr : mq.data_ptr<float>(),
-      bf16 ? u16p(tq) : nullptr, bf16 ? nullptr : tq.data_ptr<float>(),
-      actions.data_ptr<int>(), rewards.data_ptr<float>(),
-      reinterpret_cast<const unsigned char*>(done.data_ptr<bool>()),
-      weights.data_ptr<float>(),
+      m.bf16, m.f32, t.bf16, t.f32, actions.data_ptr<int>(),
+      rewards.data_ptr<float>(), boolp(done), weights.data_ptr<float>(),
       static_cast<float>(gamma), static_cast<int>(clip_mode),
       loss.data_ptr<float>(), td_st.data_ptr<float>(),
       td_out.data_ptr<float>(), B, W, A);
@@ -631,29 +425,28 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> r2d2_loss_fwd(
 torch::Tensor dueling_head_fwd(torch::Tensor h, torch::Tensor Wt,
                                torch::Tensor bt, torch::Tensor Wo,
                                torch::Tensor bo, int64_t burn) {
-  for (auto* t : {&h, &Wt, &bt, &Wo, &bo})
-    check_gpu_contig(*t, "dueling head input");
+  check_all_gpu_contig("dueling head input", h, Wt, bt, Wo, bo);
   TORCH_CHECK(h.dim() == 3 && h.scalar_type() == torch::kFloat,
               "h must be [B,L,IN] f32");
   const int B = h.size(0), L = h.size(1), IN = h.size(2);
   const int MID = Wt.size(0), AO = Wo.size(0);
   TORCH_CHECK(Wt.size(1) == IN && Wo.size(1) == MID, "weight shape");
-  TORCH_CHECK(IN <= 256 && MID <= 512 && AO <= 64 && AO >= 2,
+  TORCH_CHECK(IN <= DHEAD_MAX_IN && MID <= DHEAD_MAX_MID &&
+                  AO <= DHEAD_MAX_AO && AO >= 2,
               "dueling head dims out of range");
   const int W = L - (int)burn;
   auto q = torch::empty({B, W, AO - 1},
                         h.options().dtype(torch::kBFloat16));
-  const size_t lds = (size_t)(MID * IN + AO * MID) * 2 +
-                     (size_t)(2 * MID + 2 * IN + 2 * AO) * 4;
-  TORCH_CHECK(lds <= 160 * 1024,
+  const size_t lds = drla_dhead_fwd_lds_bytes(IN, MID, AO);
+  TORCH_CHECK(lds <= DRLA_LDS_BUDGET,
               "dueling head weights exceed the 160 KB LDS budget");
   const long long npairs = ((long long)B * W + 1) / 2;
   // few blocks, many row-pairs each: every block stages the full weight
   // set in LDS, so the grid must amortize that (~24 KB/block) over rows
   const int gx = (int)std::min<long long>((npairs + 7) / 8, 64);
   hipLaunchKernelGGL(drla_dueling_head_fwd, dim3(gx), dim3(256), lds,
-                     cur_stream(), h.data_ptr<float>(), u16p(Wt),
-                     u16p(bt), u16p(Wo), u16p(bo), u16pm(q), B, L,
+                     cur_stream(), h.data_ptr<float>(), BF16P(Wt),
+                     BF16P(bt), BF16P(Wo), BF16P(bo), BF16PM(q), B, L,
                      (int)burn, IN, MID, AO);
   return q;
 }
@@ -661,17 +454,15 @@ torch::Tensor dueling_head_fwd(torch::Tensor h, torch::Tensor Wt,
 std::tuple<torch::Tensor, torch::Tensor> dhead_train_fwd(
     torch::Tensor h, torch::Tensor Wt, torch::Tensor bt, torch::Tensor Wo,
     torch::Tensor bo) {
-  for (auto* t : {&h, &Wt, &bt, &Wo, &bo})
-    check_gpu_contig(*t, "dhead fwd input");
+  check_all_gpu_contig("dhead fwd input", h, Wt, bt, Wo, bo);
   TORCH_CHECK(h.dim() == 2 && h.scalar_type() == torch::kFloat,
               "h must be [N,IN] f32");
   const int N = h.size(0), IN = h.size(1);
   const int MID = Wt.size(0), AO = Wo.size(0);
   TORCH_CHECK(Wt.size(1) == IN && Wo.size(1) == MID && AO >= 2,
               "dhead weight shape");
-  const size_t lds = (size_t)(MID * IN + AO * MID) * 2 +
-                     (size_t)(2 * MID + 2 * IN + 2 * AO) * 4;
-  TORCH_CHECK(lds <= 160 * 1024, "dhead fwd LDS budget");
+  const size_t lds = drla_dhead_fwd_lds_bytes(IN, MID, AO);
+  TORCH_CHECK(lds <= DRLA_LDS_BUDGET, "dhead fwd LDS budget");
   auto q = torch::empty({N, AO - 1},
                         h.options().dtype(torch::kBFloat16));
   auto x_st = torch::empty({N, MID},
@@ -679,24 +470,22 @@ std::tuple<torch::Tensor, torch::Tensor> dhead_train_fwd(
   const long long npairs = ((long long)N + 1) / 2;
   const int gx = (int)std::min<long long>((npairs + 7) / 8, 64);
   hipLaunchKernelGGL(drla_dhead_train_fwd, dim3(gx), dim3(256), lds,
-                     cur_stream(), h.data_ptr<float>(), u16p(Wt), u16p(bt),
-                     u16p(Wo), u16p(bo), u16pm(q), u16pm(x_st), N, IN, MID,
-                     AO);
+                     cur_stream(), h.data_ptr<float>(), BF16P(Wt), BF16P(bt),
+                     BF16P(Wo), BF16P(bo), BF16PM(q), BF16PM(x_st), N, IN,
+                     MID, AO);
   return {q, x_st};
 }
 
 std::vector<torch::Tensor> dhead_train_bwd(
     torch::Tensor dq, torch::Tensor x_st, torch::Tensor h,
     torch::Tensor Wt, torch::Tensor Wo) {
-  for (auto* t : {&dq, &x_st, &h, &Wt, &Wo})
-    check_gpu_contig(*t, "dhead bwd input");
+  check_all_gpu_contig("dhead bwd input", dq, x_st, h, Wt, Wo);
   const int N = h.size(0), IN = h.size(1);
   const int MID = Wt.size(0), AO = Wo.size(0);
-  TORCH_CHECK(dq.scalar_type() == torch::kBFloat16, "dq must be bf16");
   const size_t lds = (size_t)(MID * IN + AO * MID) * 2 +
                      (size_t)(2 * (MID * IN + AO * MID)
                               + 2 * MID + 2 * AO + MID + IN) * 4;
-  TORCH_CHECK(lds <= 160 * 1024, "dhead bwd LDS budget");
+  TORCH_CHECK(lds <= DRLA_LDS_BUDGET, "dhead bwd LDS budget");
   auto fopt = h.options();
   auto bopt = h.options().dtype(torch::kBFloat16);
   auto dh = torch::empty({N, IN}, fopt);
@@ -705,8 +494,8 @@ std::vector<torch::Tensor> dhead_train_bwd(
   const int gx =
       (int)std::min<long long>(((long long)N + 7) / 8, 64);
   hipLaunchKernelGGL(drla_dhead_train_bwd, dim3(gx), dim3(256), lds,
-                     cur_stream(), u16p(dq), u16p(x_st),
-                     h.data_ptr<float>(), u16p(Wt), u16p(Wo),
+                     cur_stream(), BF16P(dq), BF16P(x_st),
+                     h.data_ptr<float>(), BF16P(Wt), BF16P(Wo),
                      dh.data_ptr<float>(), ws.data_ptr<float>(), N, IN,
                      MID, AO);
   auto dWt = torch::empty({MID, IN}, bopt);
@@ -715,40 +504,36 @@ std::vector<torch::Tensor> dhead_train_bwd(
   auto dbo = torch::empty({AO}, bopt);
   hipLaunchKernelGGL(drla_dhead_train_fin, dim3(drla_grid(ws_n)),
                      dim3(DRLA_BLOCK), 0, cur_stream(),
-                     ws.data_ptr<float>(), u16pm(dWt), u16pm(dbt),
-                     u16pm(dWo), u16pm(dbo), IN, MID, AO);
+                     ws.data_ptr<float>(), BF16PM(dWt), BF16PM(dbt),
+                     BF16PM(dWo), BF16PM(dbo), IN, MID, AO);
   return {dh, dWt, dbt, dWo, dbo};
 }
 
 torch::Tensor r2d2_loss_bwd(torch::Tensor td_st, torch::Tensor actions,
                             torch::Tensor weights, torch::Tensor gloss,
                             int64_t W, int64_t A, bool want_bf16) {
-  for (auto* t : {&td_st, &actions, &weights, &gloss})
-    check_gpu_contig(*t, "r2d2 bwd input");
+  check_all_gpu_contig("r2d2 bwd input", td_st, actions, weights, gloss);
   const int B = td_st.size(0);
   auto dmq = torch::empty(
       {B, W, A}, td_st.options().dtype(want_bf16 ? torch::kBFloat16
                                                  : torch::kFloat));
   const long long total = (long long)B * W * A;
+  const DualPtr out = dual_ptr(dmq);
   hipLaunchKernelGGL(drla_r2d2_loss_bwd, dim3(drla_grid(total)),
                      dim3(DRLA_BLOCK), 0, cur_stream(),
                      td_st.data_ptr<float>(), actions.data_ptr<int>(),
                      weights.data_ptr<float>(), gloss.data_ptr<float>(),
-                     want_bf16 ? u16pm(dmq) : nullptr,
-                     want_bf16 ? nullptr : dmq.data_ptr<float>(), B,
-                     (int)W, (int)A);
+                     out.bf16, out.f32, B, (int)W, (int)A);
   return dmq;
 }
 
 void per_update(torch::Tensor tree, torch::Tensor idxs,
                 torch::Tensor prios, int64_t cap) {
-  for (auto* t : {&tree, &idxs, &prios}) check_gpu_contig(*t, "per tensor");
+  check_all_gpu_contig("per tensor", tree, idxs, prios);
   TORCH_CHECK(idxs.scalar_type() == torch::kLong, "idxs must be i64");
   const int n = idxs.numel();
   hipLaunchKernelGGL(drla_per_update, dim3((n + 255) / 256), dim3(256), 0,
-                     cur_stream(), tree.data_ptr<float>(),
-                     reinterpret_cast<const long long*>(
-                         idxs.data_ptr<int64_t>()),
+                     cur_stream(), tree.data_ptr<float>(), i64p(idxs),
                      prios.data_ptr<float>(), n, cap);
 }
 
@@ -774,23 +559,15 @@ void per_rebuild(torch::Tensor tree, int64_t cap) {
 void multi_gather(torch::Tensor rows, torch::Tensor srcs,
                   torch::Tensor dsts, torch::Tensor fbytes,
                   int64_t max_chunks) {
-  for (auto* t : {&rows, &srcs, &dsts, &fbytes})
-    check_gpu_contig(*t, "multi_gather table");
+  check_all_gpu_contig("multi_gather table", rows, srcs, dsts, fbytes);
   TORCH_CHECK(rows.scalar_type() == torch::kLong, "rows must be i64");
   const int B = rows.numel();
   const int F = srcs.numel();
   const long long total = (long long)B * max_chunks;
   const int gx = (int)std::min<long long>((total + 255) / 256, 4096);
   hipLaunchKernelGGL(drla_multi_gather, dim3(gx, F), dim3(256), 0,
-                     cur_stream(),
-                     reinterpret_cast<const long long*>(
-                         rows.data_ptr<int64_t>()),
-                     reinterpret_cast<const unsigned long long*>(
-                         srcs.data_ptr<int64_t>()),
-                     reinterpret_cast<const unsigned long long*>(
-                         dsts.data_ptr<int64_t>()),
-                     reinterpret_cast<const long long*>(
-                         fbytes.data_ptr<int64_t>()), B);
+                     cur_stream(), i64p(rows), u64p(srcs), u64p(dsts),
+                     i64p(fbytes), B);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> per_sample(torch::Tensor tree,
@@ -806,8 +583,7 @@ std::tuple<torch::Tensor, torch::Tensor> per_sample(torch::Tensor tree,
   hipLaunchKernelGGL(drla_per_sample, dim3((n + 255) / 256), dim3(256), 0,
                      cur_stream(), tree.data_ptr<float>(),
                      s.data_ptr<float>(), n_entries.data_ptr<float>(),
-                     reinterpret_cast<long long*>(idx.data_ptr<int64_t>()),
-                     prio.data_ptr<float>(), n, cap);
+                     i64p(idx), prio.data_ptr<float>(), n, cap);
   return {idx, prio};
 }
 
@@ -818,7 +594,7 @@ torch::Tensor embed_bwd(torch::Tensor indices, torch::Tensor grad_out,
   TORCH_CHECK(indices.scalar_type() == torch::kLong, "indices must be i64");
   const long long N = grad_out.size(0);
   const int H = grad_out.size(1);
-  const bool in16 = grad_out.scalar_type() == torch::kBFloat16;
+  const DualPtr go = dual_ptr(grad_out);
   torch::Tensor scratch;
   if (want_bf16) {
     // persistent zero-between-calls scratch (the zeroing cast below
@@ -837,19 +613,14 @@ torch::Tensor embed_bwd(torch::Tensor indices, torch::Tensor grad_out,
   }
   hipLaunchKernelGGL(
       drla_embed_bwd_scatter, dim3(drla_grid(N * H)), dim3(DRLA_BLOCK), 0,
-      cur_stream(),
-      reinterpret_cast<const long long*>(indices.data_ptr<int64_t>()),
-      in16 ? reinterpret_cast<const unsigned short*>(grad_out.data_ptr())
-           : nullptr,
-      in16 ? nullptr : grad_out.data_ptr<float>(), scratch.data_ptr<float>(),
-      N, H, (long long)num_rows);
+      cur_stream(), i64p(indices), go.bf16, go.f32,
+      scratch.data_ptr<float>(), N, H, (long long)num_rows);
   if (!want_bf16) return scratch;
   auto out = torch::empty({num_rows, H},
                           grad_out.options().dtype(torch::kBFloat16));
   hipLaunchKernelGGL(drla_f32_to_bf16_zero_kernel,
                      dim3(drla_grid(num_rows * H)), dim3(DRLA_BLOCK), 0,
-                     cur_stream(), scratch.data_ptr<float>(),
-                     reinterpret_cast<unsigned short*>(out.data_ptr()),
+                     cur_stream(), scratch.data_ptr<float>(), BF16PM(out),
                      (long long)(num_rows * H));
   return out;
 }
@@ -858,27 +629,23 @@ std::vector<torch::Tensor> vtrace_loss_fwd(
     torch::Tensor logits, torch::Tensor value, torch::Tensor mu,
     torch::Tensor actions, torch::Tensor rewards, torch::Tensor done,
     double gamma, int64_t clip_mode, double c_bl, double c_ent) {
-  for (auto* t : {&logits, &value, &mu, &actions, &rewards, &done})
-    check_gpu_contig(*t, "vtrace_loss input");
+  check_all_gpu_contig("vtrace_loss input", logits, value, mu, actions,
+                       rewards, done);
   TORCH_CHECK(actions.scalar_type() == torch::kInt, "actions must be int32");
   TORCH_CHECK(done.scalar_type() == torch::kBool, "done must be bool");
   const int B = logits.size(0), T = logits.size(1), A = logits.size(2);
-  TORCH_CHECK(A <= 64, "num_action cap is 64");
-  const bool bf16 = logits.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(A <= VT_MAX_A, "num_action cap is ", VT_MAX_A);
+  TORCH_CHECK(T <= VT_MAX_T, "trajectory cap is ", VT_MAX_T);
+  const DualPtr lg = dual_ptr(logits);
   auto fopt = value.options().dtype(torch::kFloat);
-  TORCH_CHECK(T <= 128, "trajectory cap is 128 (VT_MAX_T)");
   auto p_stash = torch::empty({B, T, A}, fopt);
   auto vs_stash = torch::empty({B, T - 2}, fopt);
   auto adv_stash = torch::empty({B, T - 2}, fopt);
   auto losses = torch::zeros({4}, fopt);  // blocks atomicAdd into it
   hipLaunchKernelGGL(
       drla_vtrace_loss_fwd, dim3(B), dim3(256), 0, cur_stream(),
-      bf16 ? reinterpret_cast<const unsigned short*>(logits.data_ptr())
-           : nullptr,
-      bf16 ? nullptr : logits.data_ptr<float>(), value.data_ptr<float>(),
-      mu.data_ptr<float>(), actions.data_ptr<int>(),
-      rewards.data_ptr<float>(),
-      reinterpret_cast<const unsigned char*>(done.data_ptr<bool>()),
+      lg.bf16, lg.f32, value.data_ptr<float>(), mu.data_ptr<float>(),
+      actions.data_ptr<int>(), rewards.data_ptr<float>(), boolp(done),
       static_cast<float>(gamma), (int)clip_mode, static_cast<float>(c_bl),
       static_cast<float>(c_ent), p_stash.data_ptr<float>(),
       vs_stash.data_ptr<float>(), adv_stash.data_ptr<float>(),
@@ -890,24 +657,22 @@ std::tuple<torch::Tensor, torch::Tensor> vtrace_loss_bwd(
     torch::Tensor p_stash, torch::Tensor vs_stash, torch::Tensor adv_stash,
     torch::Tensor value, torch::Tensor actions, torch::Tensor grad3,
     bool from_total, double c_bl, double c_ent, bool want_bf16) {
-  for (auto* t : {&p_stash, &vs_stash, &adv_stash, &value, &actions, &grad3})
-    check_gpu_contig(*t, "vtrace_loss bwd input");
+  check_all_gpu_contig("vtrace_loss bwd input", p_stash, vs_stash,
+                       adv_stash, value, actions, grad3);
   const int B = p_stash.size(0), T = p_stash.size(1), A = p_stash.size(2);
   auto dlogits = torch::empty(
       {B, T, A},
       value.options().dtype(want_bf16 ? torch::kBFloat16 : torch::kFloat));
   auto dvalue = torch::empty({B, T}, value.options().dtype(torch::kFloat));
+  const DualPtr out = dual_ptr(dlogits);
   hipLaunchKernelGGL(
       drla_vtrace_loss_bwd, dim3(drla_grid((long long)B * T)), dim3(256), 0,
       cur_stream(), p_stash.data_ptr<float>(), vs_stash.data_ptr<float>(),
       adv_stash.data_ptr<float>(), value.data_ptr<float>(),
       actions.data_ptr<int>(), grad3.data_ptr<float>(),
       from_total ? 1 : 0, static_cast<float>(c_bl),
-      static_cast<float>(c_ent),
-      want_bf16 ? reinterpret_cast<unsigned short*>(dlogits.data_ptr())
-                : nullptr,
-      want_bf16 ? nullptr : dlogits.data_ptr<float>(),
-      dvalue.data_ptr<float>(), B, T, A);
+      static_cast<float>(c_ent), out.bf16, out.f32, dvalue.data_ptr<float>(),
+      B, T, A);
   return {dlogits, dvalue};
 }
 
@@ -930,7 +695,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_tail_fwd(
                             c_prev.options().dtype(torch::kFloat));
   if (bf16) {
     hipLaunchKernelGGL(drla_lstm_tail_fwd_bf16, dim3(drla_grid(N * H)),
-                       dim3(DRLA_BLOCK), 0, cur_stream(), u16p(gates),
+                       dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(gates),
                        c_prev.data_ptr<float>(), new_h.data_ptr<float>(),
                        new_c.data_ptr<float>(), stash.data_ptr<float>(),
                        static_cast<float>(forget_bias), N, H);
@@ -949,8 +714,7 @@ std::tuple<torch::Tensor, torch::Tensor> lstm_tail_bwd(
     torch::Tensor grad_h, c10::optional<torch::Tensor> grad_c_opt,
     torch::Tensor stash, torch::Tensor c_prev, torch::Tensor new_c,
     bool bf16_gates) {
-  for (auto* t : {&stash, &c_prev, &new_c})
-    check_gpu_contig(*t, "lstm bwd input");
+  check_all_gpu_contig("lstm bwd input", stash, c_prev, new_c);
   // grad_c is null when new_c is unused downstream (saves the zero-fill)
   const float* grad_c_ptr = nullptr;
   if (grad_c_opt.has_value()) {
@@ -972,7 +736,7 @@ std::tuple<torch::Tensor, torch::Tensor> lstm_tail_bwd(
                        dim3(DRLA_BLOCK), 0, cur_stream(),
                        grad_h.data_ptr<float>(), grad_c_ptr,
                        stash.data_ptr<float>(), c_prev.data_ptr<float>(),
-                       new_c.data_ptr<float>(), u16pm(grad_gates),
+                       new_c.data_ptr<float>(), BF16PM(grad_gates),
                        grad_c_prev.data_ptr<float>(), N, H, gh_stride);
     return {grad_gates, grad_c_prev};
   }
@@ -986,6 +750,9 @@ std::tuple<torch::Tensor, torch::Tensor> lstm_tail_bwd(
   return {grad_gates, grad_c_prev};
 }
 
+// ---- fused MLP heads, action-embedding MLP ---------------------------------
+int mh_row_tiles(int N) { return (N + MH_BM - 1) / MH_BM; }
+
 std::vector<torch::Tensor> mlp_heads_fwd(
     torch::Tensor h, std::vector<torch::Tensor> weights,
     std::vector<torch::Tensor> biases, int64_t A) {
@@ -994,22 +761,19 @@ std::vector<torch::Tensor> mlp_heads_fwd(
   for (auto& t : weights) check_gpu_contig(t, "W");
   for (auto& t : biases) check_gpu_contig(t, "b");
   const int N = h.size(0);
-  TORCH_CHECK(h.size(1) == 256 && A <= 32);
+  TORCH_CHECK(h.size(1) == MH_HID && A <= MH_MAX_A);
   auto bopt = h.options().dtype(torch::kBFloat16);
   auto logits = torch::empty({N, A}, bopt);
   auto value = torch::empty({N}, h.options().dtype(torch::kFloat));
   auto stash = torch::empty({N, 5 * 256}, bopt);
   hipLaunchKernelGGL(
-      drla_mlp_heads_fwd, dim3((N + 15) / 16, 2), dim3(256), 0,
-      cur_stream(),
-      h.data_ptr<float>(), u16p(weights[0]),
-      u16p(biases[0]), u16p(weights[1]),
-      u16p(biases[1]), u16p(weights[2]),
-      u16p(biases[2]), u16p(weights[3]),
-      u16p(biases[3]), u16p(weights[4]),
-      u16p(biases[4]), u16p(weights[5]),
-      u16p(biases[5]), u16pm(logits),
-      value.data_ptr<float>(), u16pm(stash), N, (int)A);
+      drla_mlp_heads_fwd, dim3(mh_row_tiles(N), 2), dim3(256), 0,
+      cur_stream(), h.data_ptr<float>(),
+      BF16P(weights[0]), BF16P(biases[0]), BF16P(weights[1]),
+      BF16P(biases[1]), BF16P(weights[2]), BF16P(biases[2]),
+      BF16P(weights[3]), BF16P(biases[3]), BF16P(weights[4]),
+      BF16P(biases[4]), BF16P(weights[5]), BF16P(biases[5]),
+      BF16PM(logits), value.data_ptr<float>(), BF16PM(stash), N, (int)A);
   return {logits, value, stash};
 }
 
@@ -1041,12 +805,11 @@ std::vector<torch::Tensor> mlp_heads_bwd(
   auto db2v = ws.narrow(0, off, 256); off += 256;
   auto db3v = ws.narrow(0, off, 1);
   hipLaunchKernelGGL(
-      drla_mlp_heads_bwd, dim3((N + 15) / 16, 2), dim3(256), 0,
-      cur_stream(),
-      u16p(dlogits), dvalue.data_ptr<float>(), u16p(stash),
-      u16p(weights[0]), u16p(weights[1]), u16p(weights[2]),
-      u16p(weights[3]), u16p(weights[4]), u16p(weights[5]), u16pm(dz1p),
-      u16pm(dz2p), u16pm(dz1v), u16pm(dz2v), dh.data_ptr<float>(),
+      drla_mlp_heads_bwd, dim3(mh_row_tiles(N), 2), dim3(256), 0,
+      cur_stream(), BF16P(dlogits), dvalue.data_ptr<float>(), BF16P(stash),
+      BF16P(weights[0]), BF16P(weights[1]), BF16P(weights[2]),
+      BF16P(weights[3]), BF16P(weights[4]), BF16P(weights[5]), BF16PM(dz1p),
+      BF16PM(dz2p), BF16PM(dz1v), BF16PM(dz2v), dh.data_ptr<float>(),
       db1p.data_ptr<float>(), db2p.data_ptr<float>(),
       db3p.data_ptr<float>(), db1v.data_ptr<float>(),
       db2v.data_ptr<float>(), db3v.data_ptr<float>(), N, (int)A);
@@ -1059,25 +822,23 @@ std::vector<torch::Tensor> mlp_heads_bwd(
 std::tuple<torch::Tensor, torch::Tensor> embed_mlp_fwd(
     torch::Tensor pa, torch::Tensor table, torch::Tensor b1,
     torch::Tensor w2, torch::Tensor b2) {
-  for (auto* t : {&pa, &table, &b1, &w2, &b2})
-    check_gpu_contig(*t, "embed fwd input");
+  check_all_gpu_contig("embed fwd input", pa, table, b1, w2, b2);
   TORCH_CHECK(pa.scalar_type() == torch::kLong, "pa must be int64");
   const int N = pa.numel();
   auto bopt = table.options();
   auto out = torch::empty({N, 256}, bopt);
   auto a1 = torch::empty({N, 256}, bopt);
-  hipLaunchKernelGGL(drla_embed_mlp_fwd, dim3((N + 15) / 16), dim3(256), 0,
-                     cur_stream(),
-                     reinterpret_cast<const long long*>(pa.data_ptr<int64_t>()),
-                     u16p(table), u16p(b1), u16p(w2), u16p(b2), u16pm(out),
-                     u16pm(a1), N, (int)table.size(0));
+  hipLaunchKernelGGL(drla_embed_mlp_fwd, dim3(mh_row_tiles(N)), dim3(256), 0,
+                     cur_stream(), i64p(pa), BF16P(table), BF16P(b1),
+                     BF16P(w2), BF16P(b2), BF16PM(out), BF16PM(a1), N,
+                     (int)table.size(0));
   return {out, a1};
 }
 
 std::vector<torch::Tensor> embed_mlp_bwd(torch::Tensor dy, torch::Tensor out,
                                          torch::Tensor a1, torch::Tensor w2,
                                          torch::Tensor idx, int64_t A) {
-  for (auto* t : {&out, &a1, &w2}) check_gpu_contig(*t, "embed bwd input");
+  check_all_gpu_contig("embed bwd input", out, a1, w2);
   check_gpu_contig(idx, "idx");
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 2 && dy.stride(1) == 1,
               "dy must be row-contiguous");
@@ -1092,29 +853,27 @@ std::vector<torch::Tensor> embed_mlp_bwd(torch::Tensor dy, torch::Tensor out,
     scratch = torch::zeros({n_table + 512}, bopt.dtype(torch::kFloat));
   }
   hipLaunchKernelGGL(drla_embed_w2t_pack, dim3(drla_grid(65536)),
-                     dim3(DRLA_BLOCK), 0, cur_stream(), u16p(w2),
-                     u16pm(w2t));
+                     dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(w2),
+                     BF16PM(w2t));
   auto dz2 = torch::empty({N, 256}, bopt);
   auto da1 = torch::empty({N, 256}, bopt);
   float* bias_ws = scratch.data_ptr<float>() + n_table;
-  hipLaunchKernelGGL(drla_embed_mlp_bwd, dim3((N + 15) / 16), dim3(256), 0,
-                     cur_stream(), u16p(dy), (long long)dy.stride(0),
-                     u16p(out), u16p(a1), u16p(w2t), u16pm(dz2), u16pm(da1),
-                     bias_ws, N);
+  hipLaunchKernelGGL(drla_embed_mlp_bwd, dim3(mh_row_tiles(N)), dim3(256), 0,
+                     cur_stream(), BF16P(dy), (long long)dy.stride(0),
+                     BF16P(out), BF16P(a1), BF16P(w2t), BF16PM(dz2),
+                     BF16PM(da1), bias_ws, N);
   // table scatter into the f32 scratch, then one 3-output finalize
   hipLaunchKernelGGL(
       drla_embed_bwd_scatter, dim3(drla_grid((long long)N * 256)),
-      dim3(DRLA_BLOCK), 0, cur_stream(),
-      reinterpret_cast<const long long*>(idx.data_ptr<int64_t>()),
-      u16p(da1), nullptr, scratch.data_ptr<float>(), N, 256,
-      (long long)A);
+      dim3(DRLA_BLOCK), 0, cur_stream(), i64p(idx), BF16P(da1), nullptr,
+      scratch.data_ptr<float>(), N, 256, (long long)A);
   auto dtable = torch::empty({A, 256}, bopt);
   auto db1 = torch::empty({256}, bopt);
   auto db2 = torch::empty({256}, bopt);
   hipLaunchKernelGGL(drla_embed_finalize, dim3(drla_grid(n_table + 512)),
                      dim3(DRLA_BLOCK), 0, cur_stream(),
-                     scratch.data_ptr<float>(), u16pm(dtable), u16pm(db1),
-                     u16pm(db2), n_table);
+                     scratch.data_ptr<float>(), BF16PM(dtable), BF16PM(db1),
+                     BF16PM(db2), n_table);
   return {dz2, dtable, db1, db2};
 }
 
@@ -1125,9 +884,9 @@ torch::Tensor mlp_heads_pack_wt(std::vector<torch::Tensor> weights,
   auto out = torch::empty({4 * 65536 + 256 * 32 + 256},
                           weights[0].options());
   hipLaunchKernelGGL(drla_heads_wt_pack, dim3(drla_grid(out.numel())),
-                     dim3(DRLA_BLOCK), 0, cur_stream(), u16p(weights[0]),
-                     u16p(weights[1]), u16p(weights[2]), u16p(weights[3]),
-                     u16p(weights[4]), u16p(weights[5]), u16pm(out),
+                     dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(weights[0]),
+                     BF16P(weights[1]), BF16P(weights[2]), BF16P(weights[3]),
+                     BF16P(weights[4]), BF16P(weights[5]), BF16PM(out),
                      (int)A);
   return out;
 }
@@ -1136,8 +895,8 @@ std::vector<torch::Tensor> mlp_heads_wgrad(
     torch::Tensor dz1p, torch::Tensor dz2p, torch::Tensor dz1v,
     torch::Tensor dz2v, torch::Tensor dlogits, torch::Tensor dvalue,
     torch::Tensor stash, torch::Tensor ws, int64_t A) {
-  for (auto* t : {&dz1p, &dz2p, &dz1v, &dz2v, &dlogits, &stash, &ws})
-    check_gpu_contig(*t, "wgrad input");
+  check_all_gpu_contig("wgrad input", dz1p, dz2p, dz1v, dz2v, dlogits, stash,
+                       ws);
   check_gpu_contig(dvalue, "dvalue");
   const int N = dvalue.numel();
   auto bopt = dz1p.options();
@@ -1156,39 +915,51 @@ std::vector<torch::Tensor> mlp_heads_wgrad(
   // ws tail = the f32 bias-grad partials written by mlp_heads_bwd
   const float* ws_tail = ws.data_ptr<float>() + (long long)N * 256;
   hipLaunchKernelGGL(drla_heads_wgrad, dim3(73), dim3(256), 0, cur_stream(),
-                     u16p(dz1p), u16p(dz2p), u16p(dz1v), u16p(dz2v),
-                     u16p(dlogits), dvalue.data_ptr<float>(), u16p(stash),
-                     u16pm(dw1p), u16pm(dw2p), u16pm(dw3p), u16pm(dw1v),
-                     u16pm(dw2v), u16pm(dw3v), ws_tail, u16pm(db1p),
-                     u16pm(db2p), u16pm(db3p), u16pm(db1v), u16pm(db2v),
-                     u16pm(db3v), N, (int)A);
+                     BF16P(dz1p), BF16P(dz2p), BF16P(dz1v), BF16P(dz2v),
+                     BF16P(dlogits), dvalue.data_ptr<float>(), BF16P(stash),
+                     BF16PM(dw1p), BF16PM(dw2p), BF16PM(dw3p), BF16PM(dw1v),
+                     BF16PM(dw2v), BF16PM(dw3v), ws_tail, BF16PM(db1p),
+                     BF16PM(db2p), BF16PM(db3p), BF16PM(db1v), BF16PM(db2v),
+                     BF16PM(db3v), N, (int)A);
   return {dw1p, dw2p, dw3p, dw1v, dw2v, dw3v,
           db1p, db2p, db3p, db1v, db2v, db3v};
+}
+
+// ---- LSTM sequence kernels (blockDim = 4H, Wh resident in LDS) ------------
+void check_lstm_seq_hidden(int H) {  // one thread per gate
+  TORCH_CHECK(4 * H <= LSTM_SEQ_MAX_GATES, "lstm hidden cap is ",
+              LSTM_SEQ_MAX_GATES / 4);
+}
+
+// dynamic LDS bytes of the train kernels, which have no global-memory
+// variant: Wh + carries + the gate buffer must fit one workgroup's LDS
+int lstm_seq_train_lds(int H) {
+  check_lstm_seq_hidden(H);
+  TORCH_CHECK(drla_lstm_seq_wh_fits_lds(H), "lstm seq-train kernels keep ",
+              "Wh in LDS: H=", H, " does not fit ", DRLA_LDS_BUDGET, " bytes");
+  return drla_lstm_seq_lds_bytes(H);
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_seq_fwd(
     torch::Tensor xgates, torch::Tensor Wh, torch::Tensor h0,
     torch::Tensor c0, torch::Tensor done, double forget_bias) {
-  for (auto* t : {&xgates, &Wh, &h0, &c0, &done})
-    check_gpu_contig(*t, "lstm_seq input");
-  TORCH_CHECK(Wh.scalar_type() == torch::kBFloat16, "Wh must be bf16");
+  check_all_gpu_contig("lstm_seq input", xgates, Wh, h0, c0, done);
   TORCH_CHECK(done.scalar_type() == torch::kBool, "done must be bool");
   const int B = xgates.size(0), L = xgates.size(1);
   const int H = xgates.size(2) / 4;
-  TORCH_CHECK(4 * H <= 1024, "lstm hidden cap is 256");
-  const bool bf16 = xgates.scalar_type() == torch::kBFloat16;
+  check_lstm_seq_hidden(H);
+  // a Wh too large for LDS is read from global memory instead
+  const bool wh_in_lds = drla_lstm_seq_wh_fits_lds(H);
+  const DualPtr xg = dual_ptr(xgates);
   auto fopt = h0.options().dtype(torch::kFloat);
   auto h_out = torch::empty({B, L, H}, fopt);
   auto h_fin = torch::empty({B, H}, fopt);
   auto c_fin = torch::empty({B, H}, fopt);
-  const int lds = H * 4 * H * 2 + 2 * H * 4 + 16;
   hipLaunchKernelGGL(
-      drla_lstm_seq_fwd, dim3(B), dim3(4 * H), lds, cur_stream(),
-      bf16 ? u16p(xgates) : nullptr,
-      bf16 ? nullptr : xgates.data_ptr<float>(), u16p(Wh),
-      h0.data_ptr<float>(), c0.data_ptr<float>(),
-      reinterpret_cast<const unsigned char*>(done.data_ptr<bool>()),
-      h_out.data_ptr<float>(),
+      wh_in_lds ? drla_lstm_seq_fwd : drla_lstm_seq_fwd_gmem, dim3(B),
+      dim3(4 * H), drla_lstm_seq_lds_bytes(H, wh_in_lds), cur_stream(),
+      xg.bf16, xg.f32, BF16P(Wh), h0.data_ptr<float>(), c0.data_ptr<float>(),
+      boolp(done), h_out.data_ptr<float>(),
       h_fin.data_ptr<float>(), c_fin.data_ptr<float>(),
       static_cast<float>(forget_bias), B, L, H);
   return {h_out, h_fin, c_fin};
@@ -1215,23 +986,18 @@ void grad_gather(torch::Tensor srcs, torch::Tensor offs,
   }
   hipLaunchKernelGGL(
       drla_grad_gather, dim3(drla_grid(chunks)), dim3(DRLA_BLOCK), 0,
-      cur_stream(),
-      reinterpret_cast<const unsigned long long*>(srcs.data_ptr<int64_t>()),
-      reinterpret_cast<const long long*>(offs.data_ptr<int64_t>()),
-      reinterpret_cast<const long long*>(sizes.data_ptr<int64_t>()),
-      u16pm(dst), (int)srcs.numel(), chunks, nw, nw_n);
+      cur_stream(), u64p(srcs), i64p(offs), i64p(sizes), BF16PM(dst),
+      (int)srcs.numel(), chunks, nw, nw_n);
 }
 
 std::vector<torch::Tensor> lstm_seq_train_fwd(
     torch::Tensor xg, torch::Tensor Wh, torch::Tensor h0, torch::Tensor c0,
     torch::Tensor done, double forget_bias) {
-  for (auto* t : {&xg, &Wh, &h0, &c0, &done})
-    check_gpu_contig(*t, "lstm_seq_train input");
-  TORCH_CHECK(xg.scalar_type() == torch::kBFloat16 &&
-              Wh.scalar_type() == torch::kBFloat16);
+  check_all_gpu_contig("lstm_seq_train input", xg, Wh, h0, c0, done);
   const int B = xg.size(0), L = xg.size(1), H = xg.size(2) / 4;
-  TORCH_CHECK(4 * H <= 1024 && (long long)H * 4 * H * 2 <= 120 * 1024,
-              "lstm seq-train caps: 4H<=1024 and Wh must fit LDS");
+  const int lds = lstm_seq_train_lds(H);
+  TORCH_CHECK(drla_lstm_seq_wh_elems(H) * sizeof(bf16raw) <= 120 * 1024,
+              "lstm seq-train cap: Wh must fit 120 KB of LDS");
   auto fopt = h0.options().dtype(torch::kFloat);
   auto h_out = torch::empty({B, L, H}, fopt);
   auto h_fin = torch::empty({B, H}, fopt);
@@ -1239,15 +1005,12 @@ std::vector<torch::Tensor> lstm_seq_train_fwd(
   auto acts = torch::empty({B, L, 4 * H}, fopt);
   auto c_prev = torch::empty({B, L, H}, fopt);
   auto h_prev = torch::empty({B, L, H}, xg.options());
-  const int lds = H * 4 * H * 2 + 2 * H * 4 + 16;
   hipLaunchKernelGGL(drla_lstm_seq_train_fwd, dim3(B), dim3(4 * H), lds,
-                     cur_stream(), u16p(xg), u16p(Wh),
-                     h0.data_ptr<float>(), c0.data_ptr<float>(),
-                     reinterpret_cast<const unsigned char*>(
-                         done.data_ptr<bool>()),
+                     cur_stream(), BF16P(xg), BF16P(Wh),
+                     h0.data_ptr<float>(), c0.data_ptr<float>(), boolp(done),
                      h_out.data_ptr<float>(), h_fin.data_ptr<float>(),
                      c_fin.data_ptr<float>(), acts.data_ptr<float>(),
-                     c_prev.data_ptr<float>(), u16pm(h_prev),
+                     c_prev.data_ptr<float>(), BF16PM(h_prev),
                      static_cast<float>(forget_bias), B, L, H);
   return {h_out, h_fin, c_fin, acts, c_prev, h_prev};
 }
@@ -1256,23 +1019,22 @@ std::vector<torch::Tensor> lstm_seq_train_bwd(
     torch::Tensor dh_out, c10::optional<torch::Tensor> dh_fin,
     c10::optional<torch::Tensor> dc_fin, torch::Tensor acts,
     torch::Tensor c_prev, torch::Tensor Wh, torch::Tensor done) {
-  for (auto* t : {&dh_out, &acts, &c_prev, &Wh, &done})
-    check_gpu_contig(*t, "lstm_seq_train bwd input");
+  check_all_gpu_contig("lstm_seq_train bwd input", dh_out, acts, c_prev, Wh,
+                       done);
   const int B = acts.size(0), L = acts.size(1), H = acts.size(2) / 4;
   auto fopt = dh_out.options().dtype(torch::kFloat);
   auto dxg = torch::empty({B, L, 4 * H},
                           dh_out.options().dtype(torch::kBFloat16));
   auto dh0 = torch::empty({B, H}, fopt);
   auto dc0 = torch::empty({B, H}, fopt);
-  const int lds = H * 4 * H * 2 + 2 * H * 4 + 16;
   hipLaunchKernelGGL(
-      drla_lstm_seq_train_bwd, dim3(B), dim3(4 * H), lds, cur_stream(),
-      dh_out.data_ptr<float>(),
+      drla_lstm_seq_train_bwd, dim3(B), dim3(4 * H), lstm_seq_train_lds(H),
+      cur_stream(), dh_out.data_ptr<float>(),
       dh_fin.has_value() ? dh_fin->data_ptr<float>() : nullptr,
       dc_fin.has_value() ? dc_fin->data_ptr<float>() : nullptr,
-      acts.data_ptr<float>(), c_prev.data_ptr<float>(), u16p(Wh),
-      reinterpret_cast<const unsigned char*>(done.data_ptr<bool>()),
-      u16pm(dxg), dh0.data_ptr<float>(), dc0.data_ptr<float>(), B, L, H);
+      acts.data_ptr<float>(), c_prev.data_ptr<float>(), BF16P(Wh),
+      boolp(done), BF16PM(dxg), dh0.data_ptr<float>(), dc0.data_ptr<float>(),
+      B, L, H);
   return {dxg, dh0, dc0};
 }
 
@@ -1289,12 +1051,10 @@ torch::Tensor sq_norm(torch::Tensor x) {
 
 torch::Tensor sq_norm_bf16(torch::Tensor x) {
   check_gpu_contig(x, "x");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "wants bf16");
   auto out = torch::zeros({DRLA_NORM_SLOTS * 16},
                           x.options().dtype(torch::kFloat));
   hipLaunchKernelGGL(drla_sq_norm_bf16, dim3(drla_grid(x.numel() / 4 + 1)),
-                     dim3(DRLA_BLOCK), 0, cur_stream(),
-                     reinterpret_cast<const unsigned short*>(x.data_ptr()),
+                     dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(x),
                      out.data_ptr<float>(), (long long)x.numel());
   return out;
 }
@@ -1303,11 +1063,7 @@ void rmsprop_step_bf16_t(torch::Tensor p, torch::Tensor g,
                          torch::Tensor master, torch::Tensor ms, double clip,
                          torch::Tensor lr_buf, double rho, double eps,
                          c10::optional<torch::Tensor> norm_ws) {
-  for (auto* t : {&p, &g, &master, &ms, &lr_buf})
-    check_gpu_contig(*t, "rmsprop bf16 tensor");
-  TORCH_CHECK(p.scalar_type() == torch::kBFloat16 &&
-                  g.scalar_type() == torch::kBFloat16,
-              "params/grads must be bf16");
+  check_all_gpu_contig("rmsprop bf16 tensor", p, g, master, ms, lr_buf);
   const long long n = p.numel();
   torch::Tensor norm_buf;
   if (norm_ws.has_value() && clip > 0) {
@@ -1315,8 +1071,7 @@ void rmsprop_step_bf16_t(torch::Tensor p, torch::Tensor g,
     norm_buf = *norm_ws;
     hipLaunchKernelGGL(drla_sq_norm_bf16,
                        dim3(drla_grid(g.numel() / 4 + 1)), dim3(DRLA_BLOCK),
-                       0, cur_stream(),
-                       reinterpret_cast<const unsigned short*>(g.data_ptr()),
+                       0, cur_stream(), BF16P(g),
                        norm_buf.data_ptr<float>(), (long long)g.numel());
   } else if (clip > 0) {
     norm_buf = sq_norm_bf16(g);
@@ -1324,9 +1079,7 @@ void rmsprop_step_bf16_t(torch::Tensor p, torch::Tensor g,
     norm_buf = torch::zeros({DRLA_NORM_SLOTS * 16}, master.options());
   }
   hipLaunchKernelGGL(drla_rmsprop_step_bf16, dim3(drla_grid(n)),
-                     dim3(DRLA_BLOCK), 0, cur_stream(),
-                     reinterpret_cast<unsigned short*>(p.data_ptr()),
-                     reinterpret_cast<const unsigned short*>(g.data_ptr()),
+                     dim3(DRLA_BLOCK), 0, cur_stream(), BF16PM(p), BF16P(g),
                      master.data_ptr<float>(), ms.data_ptr<float>(),
                      norm_buf.data_ptr<float>(), static_cast<float>(clip),
                      lr_buf.data_ptr<float>(), static_cast<float>(rho),
@@ -1337,8 +1090,7 @@ void adam_step_bf16_t(torch::Tensor p, torch::Tensor g, torch::Tensor master,
                       torch::Tensor m, torch::Tensor v, double clip,
                       torch::Tensor lr_buf, double beta1, double beta2,
                       double eps) {
-  for (auto* t : {&p, &g, &master, &m, &v, &lr_buf})
-    check_gpu_contig(*t, "adam bf16 tensor");
+  check_all_gpu_contig("adam bf16 tensor", p, g, master, m, v, lr_buf);
   const long long n = p.numel();
   torch::Tensor norm_buf;
   if (clip > 0) {
@@ -1347,9 +1099,7 @@ void adam_step_bf16_t(torch::Tensor p, torch::Tensor g, torch::Tensor master,
     norm_buf = torch::zeros({1}, master.options());
   }
   hipLaunchKernelGGL(drla_adam_step_bf16, dim3(drla_grid(n)),
-                     dim3(DRLA_BLOCK), 0, cur_stream(),
-                     reinterpret_cast<unsigned short*>(p.data_ptr()),
-                     reinterpret_cast<const unsigned short*>(g.data_ptr()),
+                     dim3(DRLA_BLOCK), 0, cur_stream(), BF16PM(p), BF16P(g),
                      master.data_ptr<float>(), m.data_ptr<float>(),
                      v.data_ptr<float>(), norm_buf.data_ptr<float>(),
                      static_cast<float>(clip), lr_buf.data_ptr<float>(),
@@ -1360,8 +1110,7 @@ void adam_step_bf16_t(torch::Tensor p, torch::Tensor g, torch::Tensor master,
 void rmsprop_step_t(torch::Tensor p, torch::Tensor g, torch::Tensor ms,
                     double clip, torch::Tensor lr_buf, double rho,
                     double eps) {
-  for (auto* t : {&p, &g, &ms, &lr_buf})
-    check_gpu_contig(*t, "rmsprop tensor");
+  check_all_gpu_contig("rmsprop tensor", p, g, ms, lr_buf);
   const long long n = p.numel();
   torch::Tensor norm_buf;
   if (clip > 0) {
@@ -1386,8 +1135,7 @@ void rmsprop_step(torch::Tensor p, torch::Tensor g, torch::Tensor ms,
 void adam_step_t(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                  torch::Tensor v, double clip, torch::Tensor lr_buf,
                  double beta1, double beta2, double eps) {
-  for (auto* t : {&p, &g, &m, &v, &lr_buf})
-    check_gpu_contig(*t, "adam tensor");
+  check_all_gpu_contig("adam tensor", p, g, m, v, lr_buf);
   const long long n = p.numel();
   torch::Tensor norm_buf;
   if (clip > 0) {

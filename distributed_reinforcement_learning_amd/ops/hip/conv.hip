@@ -21,11 +21,12 @@
 //   B: lane l holds B[(l>>4)*8 + e][l&15]             (8 bf16)
 //   D: lane l, reg r -> row (l>>4)*4 + r, col l&15    (4 f32)
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
-typedef unsigned short bf16raw;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
+// layer geometry (DRLA_CONV_GEOM), block size and tile sizes come from
+// drla_common.h, where the launch code reads the same values
+#define CONV_KERNEL \
+  extern "C" __global__ __launch_bounds__(DRLA_CONV_BLOCK) void
 
 __device__ __forceinline__ float cv_bf2f(bf16raw u) {
   unsigned int x = ((unsigned int)u) << 16;
@@ -66,7 +67,7 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
                               int batch,
                               IN_T* __restrict__ x_stash = nullptr) {
   constexpr int K = KH * KW * CI;
-  constexpr int BM = 128;
+  constexpr int BM = DRLA_CONV_BM;
   constexpr int BK = 32;
   constexpr int APAD = 8;
   constexpr int NFRAG = CO / 16;
@@ -109,7 +110,7 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
   bf16x8 rab0 = {0, 0, 0, 0, 0, 0, 0, 0}, rab1 = rab0;
   uint4 rbw4;
   uint2 rbw2;
-  constexpr int THREADS_PER_CO = 256 / CO;       // 8 (CO=32) or 4
+  constexpr int THREADS_PER_CO = DRLA_CONV_BLOCK / CO;  // 8 (CO=32) or 4
   constexpr int KCHUNK = BK / THREADS_PER_CO;    // 4 or 8
   const int b_co = tid / THREADS_PER_CO;
   const int b_kpart = (tid % THREADS_PER_CO) * KCHUNK;
@@ -264,33 +265,31 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
 // Bbuf[co][k] — i.e. we feed mfma(A, B^T-read) which computes A @ B with
 // B[k][col] = Bbuf[col][k]. The probe/parity tests pin this down.
 
-extern "C" __global__ __launch_bounds__(256) void drla_conv_fwd_l1(
+CONV_KERNEL drla_conv_fwd_l1(
     const unsigned char* in, const bf16raw* w, const bf16raw* bias,
     bf16raw* out, int batch, unsigned char* x_stash) {
-  conv_fwd_impl<unsigned char, 4, 32, 8, 8, 4, 84, 84, 20, 20>(
-      in, w, bias, out, batch, x_stash);
+  conv_fwd_impl<unsigned char, DRLA_CONV_GEOM(0)>(in, w, bias, out, batch,
+                                                  x_stash);
 }
 
-extern "C" __global__ __launch_bounds__(256) void drla_conv_fwd_l1_c1(
+CONV_KERNEL drla_conv_fwd_l1_c1(
     const unsigned char* in, const bf16raw* w, const bf16raw* bias,
     bf16raw* out, int batch, unsigned char* x_stash) {
   // R2D2's single-channel POMDP frames: CI=1 -> K=64; stage per-tap scalars
-  conv_fwd_impl<unsigned char, 1, 32, 8, 8, 4, 84, 84, 20, 20>(
-      in, w, bias, out, batch, x_stash);
+  conv_fwd_impl<unsigned char, DRLA_CONV_GEOM(1)>(in, w, bias, out, batch,
+                                                  x_stash);
 }
 
-extern "C" __global__ __launch_bounds__(256) void drla_conv_fwd_l2(
+CONV_KERNEL drla_conv_fwd_l2(
     const bf16raw* in, const bf16raw* w, const bf16raw* bias, bf16raw* out,
     int batch) {
-  conv_fwd_impl<bf16raw, 32, 64, 4, 4, 2, 20, 20, 9, 9>(in, w, bias, out,
-                                                        batch);
+  conv_fwd_impl<bf16raw, DRLA_CONV_GEOM(2)>(in, w, bias, out, batch);
 }
 
-extern "C" __global__ __launch_bounds__(256) void drla_conv_fwd_l3(
+CONV_KERNEL drla_conv_fwd_l3(
     const bf16raw* in, const bf16raw* w, const bf16raw* bias, bf16raw* out,
     int batch) {
-  conv_fwd_impl<bf16raw, 64, 64, 3, 3, 1, 9, 9, 7, 7>(in, w, bias, out,
-                                                      batch);
+  conv_fwd_impl<bf16raw, DRLA_CONV_GEOM(3)>(in, w, bias, out, batch);
 }
 
 // ---------------------------------------------------------------------------
@@ -369,7 +368,9 @@ extern "C" __global__ void drla_relu_mask_bwd(
     // t = g + k*(CO/8)
     float s = 0.0f;
     for (int t = g; t < DRLA_BLOCK; t += CO / 8) s += red[t * 8 + e];
-    atomicAdd(&dbias_slots[(blockIdx.x & 15) * 64 + tid], s);
+    atomicAdd(&dbias_slots[(blockIdx.x & (DRLA_DBIAS_SLOTS - 1)) *
+                               DRLA_DBIAS_STRIDE +
+                           tid], s);
   }
 }
 
@@ -384,9 +385,9 @@ extern "C" __global__ void drla_wgrad_finalize(
   // slots re-zeroed (persistent zero-between-calls buffer)
   if (dbias_slots && blockIdx.x == 0 && (int)threadIdx.x < CO) {
     float s = 0.0f;
-    for (int t = 0; t < 16; ++t) {
-      s += dbias_slots[t * 64 + threadIdx.x];
-      dbias_slots[t * 64 + threadIdx.x] = 0.0f;
+    for (int t = 0; t < DRLA_DBIAS_SLOTS; ++t) {
+      s += dbias_slots[t * DRLA_DBIAS_STRIDE + threadIdx.x];
+      dbias_slots[t * DRLA_DBIAS_STRIDE + threadIdx.x] = 0.0f;
     }
     dbias[threadIdx.x] = drla_f32_to_bf16(s);
   }
@@ -419,10 +420,11 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
                                 int batch) {
   constexpr int K = KH * KW * CI;
   constexpr int BKM = 64;   // m-rows per chunk (2 MFMA k-steps)
-  constexpr int BKK = 64;   // k-cols per block
+  constexpr int BKK = DRLA_CONV_WGRAD_BK;  // k-cols per block
   constexpr int PAD = 8;
   constexpr int NFRAG = CO / 16;
-  constexpr int CO_PER_T = (CO * 32) / 256;  // B staging: co per thread/half
+  // B staging: co per thread/half
+  constexpr int CO_PER_T = (CO * 32) / DRLA_CONV_BLOCK;
   const int M = batch * HO * WO;
 
   // Both images staged TRANSPOSED so the MFMA fragments are single
@@ -665,25 +667,21 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
   }
 }
 
-extern "C" __global__ __launch_bounds__(256) void drla_conv_wgrad_l1(
+CONV_KERNEL drla_conv_wgrad_l1(
     const unsigned char* in, const bf16raw* dy, float* scratch, int batch) {
-  conv_wgrad_impl<unsigned char, 4, 32, 8, 8, 4, 84, 84, 20, 20>(
-      in, dy, scratch, batch);
+  conv_wgrad_impl<unsigned char, DRLA_CONV_GEOM(0)>(in, dy, scratch, batch);
 }
-extern "C" __global__ __launch_bounds__(256) void drla_conv_wgrad_l1_c1(
+CONV_KERNEL drla_conv_wgrad_l1_c1(
     const unsigned char* in, const bf16raw* dy, float* scratch, int batch) {
-  conv_wgrad_impl<unsigned char, 1, 32, 8, 8, 4, 84, 84, 20, 20>(
-      in, dy, scratch, batch);
+  conv_wgrad_impl<unsigned char, DRLA_CONV_GEOM(1)>(in, dy, scratch, batch);
 }
-extern "C" __global__ __launch_bounds__(256) void drla_conv_wgrad_l2(
+CONV_KERNEL drla_conv_wgrad_l2(
     const bf16raw* in, const bf16raw* dy, float* scratch, int batch) {
-  conv_wgrad_impl<bf16raw, 32, 64, 4, 4, 2, 20, 20, 9, 9>(in, dy,
-                                                              scratch, batch);
+  conv_wgrad_impl<bf16raw, DRLA_CONV_GEOM(2)>(in, dy, scratch, batch);
 }
-extern "C" __global__ __launch_bounds__(256) void drla_conv_wgrad_l3(
+CONV_KERNEL drla_conv_wgrad_l3(
     const bf16raw* in, const bf16raw* dy, float* scratch, int batch) {
-  conv_wgrad_impl<bf16raw, 64, 64, 3, 3, 1, 9, 9, 7, 7>(in, dy, scratch,
-                                                            batch);
+  conv_wgrad_impl<bf16raw, DRLA_CONV_GEOM(3)>(in, dy, scratch, batch);
 }
 
 // ---------------------------------------------------------------------------
@@ -700,7 +698,7 @@ __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
                                 int batch) {
   constexpr int K = KH * KW * CI;
   constexpr int Kg = KH * KW * CO;
-  constexpr int BM = 128;
+  constexpr int BM = DRLA_CONV_BM;
   constexpr int BK = 32;   // kg per step: one tap x 32 co
   constexpr int PAD = 8;
   constexpr int NFRAG = CI / 16;
@@ -732,7 +730,8 @@ __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
   // during this chunk's MFMA (see wgrad note)
   uint4 rda0, rda1;
   bf16raw rbw[8];
-  constexpr int CI_PER_T = (CI * BK) / 256;  // 4 (CI=32) or 8 (CI=64)
+  // 4 (CI=32) or 8 (CI=64)
+  constexpr int CI_PER_T = (CI * BK) / DRLA_CONV_BLOCK;
   const int b_col = tid % BK;
   const int b_ci0 = (tid / BK) * CI_PER_T;
 
@@ -816,7 +815,7 @@ __device__ void conv_dgrad_s2_impl(const bf16raw* __restrict__ dy,
                                    const bf16raw* __restrict__ w,
                                    bf16raw* __restrict__ dx, int batch) {
   constexpr int K = KH * KW * CI;
-  constexpr int BM = 128;
+  constexpr int BM = DRLA_CONV_BM;
   constexpr int BK = 32;
   constexpr int PAD = 8;
   constexpr int NFRAG = CI / 16;
@@ -847,7 +846,7 @@ __device__ void conv_dgrad_s2_impl(const bf16raw* __restrict__ dy,
 
   uint4 rda0, rda1;
   bf16raw rbw[8];
-  constexpr int CI_PER_T = (CI * BK) / 256;
+  constexpr int CI_PER_T = (CI * BK) / DRLA_CONV_BLOCK;
   const int b_col = tid % BK;
   const int b_ci0 = (tid / BK) * CI_PER_T;
   constexpr int NIT = 4 * (CO / BK);
@@ -927,11 +926,14 @@ __device__ void conv_dgrad_s2_impl(const bf16raw* __restrict__ dy,
   }
 }
 
-extern "C" __global__ __launch_bounds__(256) void drla_conv_dgrad_l2(
+CONV_KERNEL drla_conv_dgrad_l2(
     const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch) {
-  conv_dgrad_s2_impl<32, 64, 4, 4, 20, 20, 9, 9>(dy, w, dx, batch);
+  constexpr DrlaConvLayer g = DRLA_CONV_LAYERS[2];
+  static_assert(g.stride == 2, "the parity-class dgrad is stride-2 only");
+  conv_dgrad_s2_impl<g.ci, g.co, g.kh, g.kw, g.hi, g.wi, g.ho, g.wo>(
+      dy, w, dx, batch);
 }
-extern "C" __global__ __launch_bounds__(256) void drla_conv_dgrad_l3(
+CONV_KERNEL drla_conv_dgrad_l3(
     const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch) {
-  conv_dgrad_impl<64, 64, 3, 3, 1, 9, 9, 7, 7>(dy, w, dx, batch);
+  conv_dgrad_impl<DRLA_CONV_GEOM(3)>(dy, w, dx, batch);
 }

@@ -8,9 +8,7 @@
 // One thread per batch row; replaces the ~12 eager launches of the torch
 // composition with one tiny kernel each way.
 
-#include "drla_common.h"
-
-typedef unsigned short bf16raw;
+#include "drla_kernels.h"
 
 __device__ __forceinline__ float dq_ld(const bf16raw* p16, const float* p32,
                                        long long i) {

@@ -6,11 +6,80 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+// ---- types shared by the kernels and their launchers ----------------------
+typedef unsigned short bf16raw;  // bf16 bit pattern
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(8))) short bf16x8;
+typedef __attribute__((ext_vector_type(4))) unsigned short ushort4v;
+
 #define DRLA_WAVE 64
 // squared-norm partials: 16 slots, each on its own 64 B cache line
 // (buffer length = 16*16 floats; slot s lives at [s*16])
 #define DRLA_NORM_SLOTS 16
+// conv bias-grad partials: drla_relu_mask_bwd spreads its atomics over
+// DRLA_DBIAS_SLOTS rows of DRLA_DBIAS_STRIDE (>= max CO) floats;
+// drla_wgrad_finalize sums and re-zeroes them
+#define DRLA_DBIAS_SLOTS 16
+#define DRLA_DBIAS_STRIDE 64
 #define DRLA_BLOCK 256
+
+// ---- shapes the host launch code and the kernels must agree on ------------
+
+// conv stack: one row per kernel family member (NHWC, VALID padding)
+struct DrlaConvLayer { int ci, co, kh, kw, stride, hi, wi, ho, wo; };
+constexpr DrlaConvLayer DRLA_CONV_LAYERS[4] = {
+    {4, 32, 8, 8, 4, 84, 84, 20, 20},   // 0: l1 (u8 x4)
+    {1, 32, 8, 8, 4, 84, 84, 20, 20},   // 1: l1_c1 (u8 x1)
+    {32, 64, 4, 4, 2, 20, 20, 9, 9},    // 2: l2
+    {64, 64, 3, 3, 1, 9, 9, 7, 7},      // 3: l3
+};
+// the nine template arguments of the conv_*_impl kernels for layer l
+#define DRLA_CONV_GEOM(l)                                               \
+  DRLA_CONV_LAYERS[l].ci, DRLA_CONV_LAYERS[l].co, DRLA_CONV_LAYERS[l].kh, \
+      DRLA_CONV_LAYERS[l].kw, DRLA_CONV_LAYERS[l].stride,               \
+      DRLA_CONV_LAYERS[l].hi, DRLA_CONV_LAYERS[l].wi,                   \
+      DRLA_CONV_LAYERS[l].ho, DRLA_CONV_LAYERS[l].wo
+#define DRLA_CONV_BLOCK 256    // threads per block, every conv kernel
+#define DRLA_CONV_BM 128       // fwd/dgrad rows per block (grid.x = M / BM)
+#define DRLA_CONV_WGRAD_BK 64  // wgrad k-rows per block (grid.x = K / BK)
+
+// fused V-trace loss: T sizes the LDS scan buffers, A is the softmax width
+#define VT_MAX_T 128
+#define VT_MAX_A 64
+
+// fused MLP heads / action-embedding MLP: hidden width and rows per block
+#define MH_HID 256
+#define MH_BM 16
+#define MH_MAX_A 32  // policy out layer is one padded 32-column tile
+
+// dueling heads (r2d2_loss.hip): dim caps of the no-grad head, and the
+// dynamic LDS of the no-grad / train-fwd kernels — bf16 Wt [MID][IN] and
+// Wo [AO][MID], then f32 x [2][MID], h [2][IN], y [2][AO]
+#define DHEAD_MAX_IN 256
+#define DHEAD_MAX_MID 512
+#define DHEAD_MAX_AO 64
+#define DRLA_LDS_BUDGET (160 * 1024)
+constexpr size_t drla_dhead_fwd_lds_bytes(int IN, int MID, int AO) {
+  return (size_t)(MID * IN + AO * MID) * sizeof(bf16raw) +
+         (size_t)(2 * MID + 2 * IN + 2 * AO) * sizeof(float);
+}
+
+// LSTM sequence kernels: blockDim = 4H gates, capped by the block size;
+// static LDS = one f32 per gate; dynamic LDS = bf16 Wh [H][4H], then two
+// f32 [H] carries (+16 B slack). drla_lstm_seq_fwd_gmem leaves Wh in global
+// memory for a hidden size whose Wh does not fit.
+#define LSTM_SEQ_MAX_GATES 1024
+#define LSTM_SEQ_STATIC_LDS_BYTES (LSTM_SEQ_MAX_GATES * (int)sizeof(float))
+constexpr int drla_lstm_seq_wh_elems(int H) { return H * 4 * H; }
+constexpr int drla_lstm_seq_lds_bytes(int H, bool wh_in_lds = true) {
+  return (wh_in_lds ? drla_lstm_seq_wh_elems(H) * (int)sizeof(bf16raw) : 0) +
+         2 * H * (int)sizeof(float) + 16;
+}
+constexpr bool drla_lstm_seq_wh_fits_lds(int H) {
+  return drla_lstm_seq_lds_bytes(H) + LSTM_SEQ_STATIC_LDS_BYTES <=
+         DRLA_LDS_BUDGET;
+}
+
 // cap grids at ~8 blocks/CU x 256 CUs and grid-stride the rest
 #define DRLA_MAX_BLOCKS 2048
 

@@ -5,7 +5,7 @@
 // 64/32 bytes, so a wave moves 1 KiB of input per instruction — the
 // coalescing sweet spot (guide §2). Grid-stride, blocks of 256 (4 waves).
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
 extern "C" __global__ void drla_u8_normalize_f32(
     const uchar4* __restrict__ in, float4* __restrict__ out, long long n4) {
@@ -19,7 +19,6 @@ extern "C" __global__ void drla_u8_normalize_f32(
 }
 
 typedef __attribute__((ext_vector_type(4))) unsigned int uint4v;
-typedef __attribute__((ext_vector_type(4))) unsigned short ushort4v;
 
 extern "C" __global__ void drla_u8_normalize_bf16(
     const uchar4* __restrict__ in, ushort4v* __restrict__ out, long long n4) {

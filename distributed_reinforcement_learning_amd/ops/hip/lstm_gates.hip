@@ -9,15 +9,12 @@
 // Layout: gates [N, 4H] row-major, states [N, H]. One lane per (n, h) cell;
 // fully coalesced; stash holds the post-activation gates for backward.
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
-typedef unsigned short lstm_bf16;
-
-__device__ __forceinline__ float lstm_b2f(lstm_bf16 u) {
+__device__ __forceinline__ float lstm_b2f(bf16raw u) {
   unsigned int x = ((unsigned int)u) << 16;
   return __uint_as_float(x);
 }
-
 
 extern "C" __global__ void drla_lstm_tail_fwd(
     const float* __restrict__ gates, const float* __restrict__ c_prev,
@@ -80,7 +77,6 @@ extern "C" __global__ void drla_lstm_tail_bwd(
     grad_gates[g0 + 3 * H] = do_ * o_s * (1.0f - o_s);
   }
 }
-
 
 // bf16-gates variants: the gate GEMM (addmm) emits bf16; reading it
 // directly (and emitting bf16 grad_gates) removes the [N,4H] f32 cast
@@ -153,15 +149,18 @@ extern "C" __global__ void drla_lstm_tail_bwd_bf16(
 // One block per batch row: Wh [H][4H] staged in LDS once, then L steps of
 // {gates_h = h @ Wh + xgates[t]; cell tail; done-mask reset} with h/c in
 // LDS. blockDim = 4H (H=64 -> 256 threads); consecutive lanes read
-// consecutive Wh bytes (conflict-free).
+// consecutive Wh bytes (conflict-free). A hidden size whose Wh is larger
+// than LDS (H > 140, up to the 4H <= 1024 block cap) runs the same body
+// with Wh read from global memory, where its <= 512 KB stay L2-resident.
 //
 // Replaces the reference's per-timestep replica chain
 // (r2d2_lstm.py:67-114): ~5 launches/step -> 1 launch per sequence.
 
-extern "C" __global__ void drla_lstm_seq_fwd(
-    const lstm_bf16* __restrict__ xg16,  // [B,L,4H] (nullable)
+template <bool WH_IN_LDS>
+__device__ __forceinline__ void lstm_seq_fwd_impl(
+    const bf16raw* __restrict__ xg16,  // [B,L,4H] (nullable)
     const float* __restrict__ xg32,      // [B,L,4H] (nullable)
-    const lstm_bf16* __restrict__ Wh,    // [H][4H] bf16
+    const bf16raw* __restrict__ Wh,    // [H][4H] bf16
     const float* __restrict__ h0,        // [B,H]
     const float* __restrict__ c0,        // [B,H]
     const unsigned char* __restrict__ done,  // [B,L]
@@ -170,15 +169,19 @@ extern "C" __global__ void drla_lstm_seq_fwd(
     float* __restrict__ c_fin,           // [B,H]
     float forget_bias, int B, int L, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  lstm_bf16* wh = reinterpret_cast<lstm_bf16*>(smem);        // [H*4H]
-  float* hbuf = reinterpret_cast<float*>(wh + H * 4 * H);    // [H]
+  bf16raw* wh_lds = reinterpret_cast<bf16raw*>(smem);    // [H*4H] or empty
+  float* hbuf = reinterpret_cast<float*>(
+      wh_lds + (WH_IN_LDS ? drla_lstm_seq_wh_elems(H) : 0));
   float* cbuf = hbuf + H;                                    // [H]
 
   const int b = blockIdx.x;
   const int j = threadIdx.x;          // gate index in [0, 4H)
   const int G = 4 * H;
 
-  for (int i = j; i < H * G; i += blockDim.x) wh[i] = Wh[i];
+  if (WH_IN_LDS) {
+    for (int i = j; i < H * G; i += blockDim.x) wh_lds[i] = Wh[i];
+  }
+  const bf16raw* wh = WH_IN_LDS ? wh_lds : Wh;
   if (j < H) {
     hbuf[j] = h0[(long long)b * H + j];
     cbuf[j] = c0[(long long)b * H + j];
@@ -193,7 +196,8 @@ extern "C" __global__ void drla_lstm_seq_fwd(
     }
     const long long xbase = ((long long)b * L + t) * G + j;
     g += xg16 ? lstm_b2f(xg16[xbase]) : xg32[xbase];
-    __shared__ float gates[1024];
+    __shared__ float gates[LSTM_SEQ_MAX_GATES];
+    static_assert(sizeof(gates) == LSTM_SEQ_STATIC_LDS_BYTES, "LDS budget");
     gates[j] = g;
     __syncthreads();
     if (j < H) {
@@ -217,6 +221,26 @@ extern "C" __global__ void drla_lstm_seq_fwd(
   }
 }
 
+extern "C" __global__ void drla_lstm_seq_fwd(
+    const bf16raw* __restrict__ xg16, const float* __restrict__ xg32,
+    const bf16raw* __restrict__ Wh, const float* __restrict__ h0,
+    const float* __restrict__ c0, const unsigned char* __restrict__ done,
+    float* __restrict__ h_out, float* __restrict__ h_fin,
+    float* __restrict__ c_fin, float forget_bias, int B, int L, int H) {
+  lstm_seq_fwd_impl<true>(xg16, xg32, Wh, h0, c0, done, h_out, h_fin, c_fin,
+                          forget_bias, B, L, H);
+}
+
+extern "C" __global__ void drla_lstm_seq_fwd_gmem(
+    const bf16raw* __restrict__ xg16, const float* __restrict__ xg32,
+    const bf16raw* __restrict__ Wh, const float* __restrict__ h0,
+    const float* __restrict__ c0, const unsigned char* __restrict__ done,
+    float* __restrict__ h_out, float* __restrict__ h_fin,
+    float* __restrict__ c_fin, float forget_bias, int B, int L, int H) {
+  lstm_seq_fwd_impl<false>(xg16, xg32, Wh, h0, c0, done, h_out, h_fin, c_fin,
+                           forget_bias, B, L, H);
+}
+
 // ---------------------------------------------------------------------------
 // K3 sequence form WITH GRADIENTS: the R2D2 trained window currently loops
 // L per-step cell calls (~6 launches each + backward). This pair runs the
@@ -227,8 +251,8 @@ extern "C" __global__ void drla_lstm_seq_fwd(
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ void drla_lstm_seq_train_fwd(
-    const lstm_bf16* __restrict__ xg16,  // [B,L,4H]
-    const lstm_bf16* __restrict__ Wh,    // [H][4H]
+    const bf16raw* __restrict__ xg16,  // [B,L,4H]
+    const bf16raw* __restrict__ Wh,    // [H][4H]
     const float* __restrict__ h0,        // [B,H]
     const float* __restrict__ c0,        // [B,H]
     const unsigned char* __restrict__ done,  // [B,L]
@@ -236,11 +260,11 @@ extern "C" __global__ void drla_lstm_seq_train_fwd(
     float* __restrict__ h_fin, float* __restrict__ c_fin,  // [B,H]
     float* __restrict__ acts,            // [B,L,4H] i,g,f,o activated
     float* __restrict__ c_prev_st,       // [B,L,H]
-    lstm_bf16* __restrict__ h_prev_st,   // [B,L,H]
+    bf16raw* __restrict__ h_prev_st,   // [B,L,H]
     float forget_bias, int B, int L, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  lstm_bf16* wh = reinterpret_cast<lstm_bf16*>(smem);
-  float* hbuf = reinterpret_cast<float*>(wh + H * 4 * H);
+  bf16raw* wh = reinterpret_cast<bf16raw*>(smem);
+  float* hbuf = reinterpret_cast<float*>(wh + drla_lstm_seq_wh_elems(H));
   float* cbuf = hbuf + H;
 
   const int b = blockIdx.x;
@@ -261,7 +285,8 @@ extern "C" __global__ void drla_lstm_seq_train_fwd(
     }
     const long long xbase = ((long long)b * L + t) * G + j;
     g += lstm_b2f(xg16[xbase]);
-    __shared__ float gates[1024];
+    __shared__ float gates[LSTM_SEQ_MAX_GATES];
+    static_assert(sizeof(gates) == LSTM_SEQ_STATIC_LDS_BYTES, "LDS budget");
     gates[j] = g;
     __syncthreads();
     if (j < H) {
@@ -297,14 +322,14 @@ extern "C" __global__ void drla_lstm_seq_train_bwd(
     const float* __restrict__ dc_fin,    // [B,H] or null
     const float* __restrict__ acts,      // [B,L,4H]
     const float* __restrict__ c_prev_st, // [B,L,H]
-    const lstm_bf16* __restrict__ Wh,    // [H][4H]
+    const bf16raw* __restrict__ Wh,    // [H][4H]
     const unsigned char* __restrict__ done,  // [B,L]
-    lstm_bf16* __restrict__ dxg,         // [B,L,4H] gate-preact grads
+    bf16raw* __restrict__ dxg,         // [B,L,4H] gate-preact grads
     float* __restrict__ dh0, float* __restrict__ dc0,  // [B,H]
     int B, int L, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  lstm_bf16* wh = reinterpret_cast<lstm_bf16*>(smem);
-  float* dhc = reinterpret_cast<float*>(wh + H * 4 * H);  // [H]
+  bf16raw* wh = reinterpret_cast<bf16raw*>(smem);
+  float* dhc = reinterpret_cast<float*>(wh + drla_lstm_seq_wh_elems(H));
   float* dcc = dhc + H;                                   // [H]
 
   const int b = blockIdx.x;
@@ -318,7 +343,8 @@ extern "C" __global__ void drla_lstm_seq_train_bwd(
   }
   __syncthreads();
 
-  __shared__ float dg4[1024];
+  __shared__ float dg4[LSTM_SEQ_MAX_GATES];
+  static_assert(sizeof(dg4) == LSTM_SEQ_STATIC_LDS_BYTES, "LDS budget");
   for (int t = L - 1; t >= 0; --t) {
     const float keep = done[(long long)b * L + t] ? 0.0f : 1.0f;
     if (j < H) {

@@ -19,14 +19,10 @@
 // copies), fusing ReLU masks and bias gradients; only the six
 // MFMA-efficient wgrad GEMMs stay on hipBLASLt.
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
-typedef unsigned short bf16raw;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-
-#define MH_HID 256
-#define MH_BM 16
+// MH_HID (hidden width) and MH_BM (rows per block) are in drla_common.h:
+// the launch grids are computed from them
 #define MH_PAD 8
 #define MH_LD (MH_HID + MH_PAD)
 
@@ -143,7 +139,6 @@ __device__ void mh_pass(const bf16raw (*act_in)[MH_LD],
   }
   __syncthreads();
 }
-
 
 extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
     const float* __restrict__ h,        // [N,256]

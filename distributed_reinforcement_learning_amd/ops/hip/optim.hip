@@ -9,7 +9,7 @@
 // The clip scale is computed on-device from the norm result (no host sync):
 // scale = clip / max(norm, clip), passed as a 1-element tensor.
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
 extern "C" __global__ void drla_sq_norm(
     const float* __restrict__ x, float* __restrict__ out, long long n) {

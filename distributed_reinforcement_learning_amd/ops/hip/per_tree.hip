@@ -11,7 +11,7 @@
 // the root. O(log cap) atomics per update, batched.
 // sample: one thread per query — root-to-leaf descent.
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
 extern "C" __global__ void drla_per_update(
     float* __restrict__ tree, const long long* __restrict__ idxs,

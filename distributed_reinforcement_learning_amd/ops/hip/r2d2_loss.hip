@@ -24,11 +24,9 @@
 // detached, argmax is piecewise-constant):
 //   dQm[b,t,a] = gloss * w_b * (-2 td_t) / ((W-1) * B) * [a == act_t]
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
-typedef unsigned short r2_bf16;
-
-__device__ __forceinline__ float r2_ld(const r2_bf16* p16, const float* p32,
+__device__ __forceinline__ float r2_ld(const bf16raw* p16, const float* p32,
                                        long long i) {
   if (p16) {
     unsigned int x = ((unsigned int)p16[i]) << 16;
@@ -61,8 +59,8 @@ __device__ __forceinline__ float r2_hinv(float x) {
 }
 
 extern "C" __global__ void drla_r2d2_loss_fwd(
-    const r2_bf16* __restrict__ mq16, const float* __restrict__ mq32,
-    const r2_bf16* __restrict__ tq16, const float* __restrict__ tq32,
+    const bf16raw* __restrict__ mq16, const float* __restrict__ mq32,
+    const bf16raw* __restrict__ tq16, const float* __restrict__ tq32,
     const int* __restrict__ actions,     // [B,W]
     const float* __restrict__ rewards,   // [B,W] raw
     const unsigned char* __restrict__ done,  // [B,W]
@@ -121,15 +119,15 @@ extern "C" __global__ void drla_r2d2_loss_fwd(
 // [out][in] row-major.
 extern "C" __global__ void drla_dueling_head_fwd(
     const float* __restrict__ h,       // [B, L, IN]
-    const r2_bf16* __restrict__ Wt,    // [MID][IN]
-    const r2_bf16* __restrict__ bt,    // [MID]
-    const r2_bf16* __restrict__ Wo,    // [AO][MID]
-    const r2_bf16* __restrict__ bo,    // [AO]
-    r2_bf16* __restrict__ q,           // [B, W, AO-1]
+    const bf16raw* __restrict__ Wt,    // [MID][IN]
+    const bf16raw* __restrict__ bt,    // [MID]
+    const bf16raw* __restrict__ Wo,    // [AO][MID]
+    const bf16raw* __restrict__ bo,    // [AO]
+    bf16raw* __restrict__ q,           // [B, W, AO-1]
     int B, int L, int burn, int IN, int MID, int AO) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  r2_bf16* wt = reinterpret_cast<r2_bf16*>(smem);          // [MID*IN]
-  r2_bf16* wo = wt + MID * IN;                             // [AO*MID]
+  bf16raw* wt = reinterpret_cast<bf16raw*>(smem);          // [MID*IN]
+  bf16raw* wo = wt + MID * IN;                             // [AO*MID]
   float* xb = reinterpret_cast<float*>(wo + AO * MID);     // [2][MID]
   float* hb = xb + 2 * MID;                                // [2][IN]
   float* yb = hb + 2 * IN;                                 // [2][AO]
@@ -156,7 +154,7 @@ extern "C" __global__ void drla_dueling_head_fwd(
     if (live) {
       for (int o = lane; o < MID; o += 128) {
         float acc = r2_ld(bt, nullptr, o);
-        const r2_bf16* wrow = wt + o * IN;
+        const bf16raw* wrow = wt + o * IN;
         for (int i = 0; i < IN; ++i)
           acc = fmaf(hb[half * IN + i], r2_ld(wrow, nullptr, i), acc);
         xb[half * MID + o] = fmaxf(acc, 0.0f);
@@ -165,7 +163,7 @@ extern "C" __global__ void drla_dueling_head_fwd(
     __syncthreads();
     if (live && lane < AO) {
       float acc = r2_ld(bo, nullptr, lane);
-      const r2_bf16* wrow = wo + lane * MID;
+      const bf16raw* wrow = wo + lane * MID;
       for (int i = 0; i < MID; ++i)
         acc = fmaf(xb[half * MID + i], r2_ld(wrow, nullptr, i), acc);
       yb[half * AO + lane] = acc;
@@ -184,7 +182,7 @@ extern "C" __global__ void drla_r2d2_loss_bwd(
     const int* __restrict__ actions,   // [B,W]
     const float* __restrict__ weights, // [B]
     const float* __restrict__ gloss,   // [1]
-    r2_bf16* __restrict__ dmq16, float* __restrict__ dmq32,
+    bf16raw* __restrict__ dmq16, float* __restrict__ dmq32,
     int B, int W, int A) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   const long long total = (long long)B * W * A;
@@ -223,16 +221,16 @@ extern "C" __global__ void drla_r2d2_loss_bwd(
 
 extern "C" __global__ void drla_dhead_train_fwd(
     const float* __restrict__ h,       // [N, IN]
-    const r2_bf16* __restrict__ Wt,    // [MID][IN]
-    const r2_bf16* __restrict__ bt,    // [MID]
-    const r2_bf16* __restrict__ Wo,    // [AO][MID]
-    const r2_bf16* __restrict__ bo,    // [AO]
-    r2_bf16* __restrict__ q,           // [N, AO-1]
-    r2_bf16* __restrict__ x_st,        // [N, MID] post-ReLU stash
+    const bf16raw* __restrict__ Wt,    // [MID][IN]
+    const bf16raw* __restrict__ bt,    // [MID]
+    const bf16raw* __restrict__ Wo,    // [AO][MID]
+    const bf16raw* __restrict__ bo,    // [AO]
+    bf16raw* __restrict__ q,           // [N, AO-1]
+    bf16raw* __restrict__ x_st,        // [N, MID] post-ReLU stash
     int N, int IN, int MID, int AO) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  r2_bf16* wt = reinterpret_cast<r2_bf16*>(smem);
-  r2_bf16* wo = wt + MID * IN;
+  bf16raw* wt = reinterpret_cast<bf16raw*>(smem);
+  bf16raw* wo = wt + MID * IN;
   float* xb = reinterpret_cast<float*>(wo + AO * MID);     // [2][MID]
   float* hb = xb + 2 * MID;                                // [2][IN]
   float* yb = hb + 2 * IN;                                 // [2][AO]
@@ -257,7 +255,7 @@ extern "C" __global__ void drla_dhead_train_fwd(
     if (live) {
       for (int o = lane; o < MID; o += 128) {
         float acc = r2_ld(bt, nullptr, o);
-        const r2_bf16* wrow = wt + o * IN;
+        const bf16raw* wrow = wt + o * IN;
         for (int i = 0; i < IN; ++i)
           acc = fmaf(hb[half * IN + i], r2_ld(wrow, nullptr, i), acc);
         const float x = fmaxf(acc, 0.0f);
@@ -268,7 +266,7 @@ extern "C" __global__ void drla_dhead_train_fwd(
     __syncthreads();
     if (live && lane < AO) {
       float acc = r2_ld(bo, nullptr, lane);
-      const r2_bf16* wrow = wo + lane * MID;
+      const bf16raw* wrow = wo + lane * MID;
       for (int i = 0; i < MID; ++i)
         acc = fmaf(xb[half * MID + i], r2_ld(wrow, nullptr, i), acc);
       yb[half * AO + lane] = acc;
@@ -283,18 +281,18 @@ extern "C" __global__ void drla_dhead_train_fwd(
 }
 
 extern "C" __global__ void drla_dhead_train_bwd(
-    const r2_bf16* __restrict__ dq,    // [N, AO-1]
-    const r2_bf16* __restrict__ x_st,  // [N, MID]
+    const bf16raw* __restrict__ dq,    // [N, AO-1]
+    const bf16raw* __restrict__ x_st,  // [N, MID]
     const float* __restrict__ h,       // [N, IN]
-    const r2_bf16* __restrict__ Wt,    // [MID][IN]
-    const r2_bf16* __restrict__ Wo,    // [AO][MID]
+    const bf16raw* __restrict__ Wt,    // [MID][IN]
+    const bf16raw* __restrict__ Wo,    // [AO][MID]
     float* __restrict__ dh,            // [N, IN] f32
     float* __restrict__ ws,            // [MID*IN + MID + AO*MID + AO],
                                        // zeroed: dWt | dbt | dWo | dbo
     int N, int IN, int MID, int AO) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  r2_bf16* wt = reinterpret_cast<r2_bf16*>(smem);          // [MID*IN]
-  r2_bf16* wo = wt + MID * IN;                             // [AO*MID]
+  bf16raw* wt = reinterpret_cast<bf16raw*>(smem);          // [MID*IN]
+  bf16raw* wo = wt + MID * IN;                             // [AO*MID]
   float* lWt = reinterpret_cast<float*>(wo + AO * MID);    // [MID*IN]
   float* lWo = lWt + MID * IN;                             // [AO*MID]
   float* lbt = lWo + AO * MID;                             // [MID]
@@ -379,13 +377,13 @@ extern "C" __global__ void drla_dhead_train_bwd(
 }
 
 extern "C" __global__ void drla_dhead_train_fin(
-    const float* __restrict__ ws, r2_bf16* __restrict__ dWt,
-    r2_bf16* __restrict__ dbt, r2_bf16* __restrict__ dWo,
-    r2_bf16* __restrict__ dbo, int IN, int MID, int AO) {
+    const float* __restrict__ ws, bf16raw* __restrict__ dWt,
+    bf16raw* __restrict__ dbt, bf16raw* __restrict__ dWo,
+    bf16raw* __restrict__ dbo, int IN, int MID, int AO) {
   const int total = MID * IN + MID + AO * MID + AO;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += gridDim.x * blockDim.x) {
-    const r2_bf16 v = drla_f32_to_bf16(ws[i]);
+    const bf16raw v = drla_f32_to_bf16(ws[i]);
     if (i < MID * IN) dWt[i] = v;
     else if (i < MID * IN + MID) dbt[i - MID * IN] = v;
     else if (i < MID * IN + MID + AO * MID)

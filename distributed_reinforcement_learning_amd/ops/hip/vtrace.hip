@@ -7,7 +7,7 @@
 // (vtrace.py:88-100). Row-major [B,T] layout: a lane walks its row backwards
 // with stride 1 (per-lane sequential, L2-resident).
 
-#include "drla_common.h"
+#include "drla_kernels.h"
 
 extern "C" __global__ void drla_vtrace_scan(
     const float* __restrict__ deltas, const float* __restrict__ discounts,

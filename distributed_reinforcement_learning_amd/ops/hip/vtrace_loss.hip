@@ -16,18 +16,16 @@
 // Replaces ~90 eager launches (~400 us/step measured,
 // profiles/impala_bench_r06_bf16_kernels.md) with two small kernels.
 
-#include "drla_common.h"
-
-typedef unsigned short bf16raw;
+#include "drla_kernels.h"
 
 __device__ __forceinline__ float vt_ld(const bf16raw* p, long long i) {
   unsigned int x = ((unsigned int)p[i]) << 16;
   return __uint_as_float(x);
 }
 
-#define VT_MAX_T 128  // trajectory-length cap for the LDS scan buffers
-
 // grid = B blocks of 256; losses[4] must be ZERO on entry (atomicAdd).
+// T <= VT_MAX_T (drla_common.h; the launcher checks it): it sizes the LDS
+// scan buffers below.
 // Reward clipping (clip_mode: 0 = abs_one, 1 = soft_asymmetric, 2 = none,
 // reference agent/impala.py:45-49) and discounts = (1-done)*gamma are
 // computed IN-KERNEL from the raw reward/done rows — the python-side

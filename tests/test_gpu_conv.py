@@ -72,6 +72,92 @@ def test_conv_fwd_layer_parity(ext, layer, ci, co, k, s, hi, ho, u8):
     assert (y.float() >= 0).all()  # fused ReLU
 
 
+def _rel_mean_err(got, ref, floor):
+    return ((got.float() - ref).abs().mean()
+            / ref.abs().mean().clamp(min=floor)).item()
+
+
+@pytest.mark.parametrize("batch", [1, 3])
+@pytest.mark.parametrize("layer,ci,co,k,s,hi,ho,u8", [
+    (0, 4, 32, 8, 4, 84, 20, True),
+    (1, 1, 32, 8, 4, 84, 20, True),
+    (2, 32, 64, 4, 2, 20, 9, False),
+    (3, 64, 64, 3, 1, 9, 7, False),
+])
+def test_conv_layer_kernels_ragged_last_tile(ext, layer, ci, co, k, s, hi,
+                                             ho, u8, batch):
+    """fwd, wgrad (+ bias grad) and dgrad of every layer index, called
+    directly, at batches whose row count is not a multiple of the 128-row
+    tile (batch 1: layer 3 M = 49, layer 2 M = 81): the per-layer geometry
+    table and the kernel-pointer dispatch, l1_c1 included.
+
+    Bounds are the ones this file already uses: 0.03 forward, 0.08 weight
+    grad, 0.12 bias grad. The backward reference differentiates an fp32
+    conv with the SAME bf16-rounded weights at the kernel's own masked dy,
+    so the only error left is f32 accumulation order and the bf16 rounding
+    of the outputs (2^-9 relative) — dgrad is held to the forward's 0.03,
+    which additionally allows for weight rounding the reference here does
+    not even have."""
+    torch.manual_seed(10 * layer + batch)
+    conv = torch.nn.Conv2d(ci, co, k, stride=s).cuda()
+    conv_bf = torch.nn.Conv2d(ci, co, k, stride=s).cuda()
+    conv_bf.load_state_dict(conv.state_dict())
+    conv_bf = conv_bf.to(torch.bfloat16).to(
+        memory_format=torch.channels_last)
+    if u8:
+        x_in = torch.randint(0, 256, (batch, hi, hi, ci), dtype=torch.uint8,
+                             device="cuda")
+        x_ref = x_in.float() / 255.0
+    else:
+        x_in = torch.randn(batch, hi, hi, ci, device="cuda").bfloat16() * 0.5
+        x_ref = x_in.float()
+    w_flat = conv_bf.weight.permute(0, 2, 3, 1).reshape(co, -1).contiguous()
+    assert (batch * ho * ho) % 128 != 0
+
+    y, _ = ext.conv_fwd(layer, x_in.contiguous(), w_flat,
+                        conv_bf.bias.contiguous(), False)
+    assert y.shape == (batch, ho, ho, co)
+    ref = _torch_conv_nhwc(x_ref, conv)
+    assert _rel_mean_err(y, ref, 1e-3) < 0.03, f"layer {layer} fwd"
+    assert (y.float() >= 0).all()  # fused ReLU
+
+    dy = torch.randn(batch, ho, ho, co, device="cuda").bfloat16()
+    dy_m = ext.relu_mask_bwd(dy, y, co, layer)
+    assert torch.equal(dy_m.float(), dy.float() * (y.float() > 0))
+    dw, dbias = ext.conv_wgrad(layer, x_in.contiguous(), dy_m)
+    assert dw.shape == (co, k * k * ci) and dbias.shape == (co,)
+
+    x_g = x_ref.clone().requires_grad_(True)
+    w_g = conv_bf.weight.float().contiguous().requires_grad_(True)
+    b_g = conv_bf.bias.float().requires_grad_(True)
+    pre = F.conv2d(x_g.permute(0, 3, 1, 2), w_g, b_g, stride=s)
+    gx, gw, gb = torch.autograd.grad(
+        pre, [x_g, w_g, b_g], dy_m.float().permute(0, 3, 1, 2))
+    gw_flat = gw.permute(0, 2, 3, 1).reshape(co, -1)
+    assert _rel_mean_err(dw, gw_flat, 1e-4) < 0.08, f"layer {layer} wgrad"
+    assert _rel_mean_err(dbias, gb, 1e-4) < 0.12, f"layer {layer} dbias"
+    if layer >= 2:
+        dx = ext.conv_dgrad(layer, dy_m, w_flat)
+        assert dx.shape == (batch, hi, hi, ci)
+        assert _rel_mean_err(dx, gx, 1e-3) < 0.03, f"layer {layer} dgrad"
+
+
+def test_conv_fwd_refuses_non_bf16_operands(ext):
+    """A float32 tensor where bf16 bits are expected used to be
+    reinterpreted silently. float32 is WIDER than bf16, so a missing check
+    could only misread inside the buffer."""
+    co, K = 64, 3 * 3 * 64
+    x = torch.zeros(1, 9, 9, 64, device="cuda", dtype=torch.bfloat16)
+    w = torch.zeros(co, K, device="cuda", dtype=torch.bfloat16)
+    b = torch.zeros(co, device="cuda", dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match=r"\bin must be bf16"):
+        ext.conv_fwd(3, x.float(), w, b, False)
+    with pytest.raises(RuntimeError, match=r"\bw must be bf16"):
+        ext.conv_fwd(3, x, w.float(), b, False)
+    y, _ = ext.conv_fwd(3, x, w, b, False)  # the valid call still runs
+    assert y.shape == (1, 7, 7, 64)
+
+
 def test_full_stack_forward_and_backward_parity():
     """Custom stack (fwd+bwd) vs torch fp32 reference with identical
     weights; gradients compared with bf16 tolerances."""

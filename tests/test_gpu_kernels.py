@@ -336,11 +336,78 @@ def test_fused_action_embed_parity(ext):
 
 @pytest.mark.parametrize("L", [9, 40, 80])  # 80 = BASELINE seq_len (config #4)
 def test_lstm_seq_train_parity(ext, L):
+    _check_lstm_seq_train(5, 64, L)
+
+
+# The sequence kernels keep Wh [H][4H] bf16 in dynamic LDS, sized on the
+# host by drla_lstm_seq_lds_bytes(H) and carved up in the kernels: a
+# mismatch shows as a wrong carry. H = 64 is what the tests above use; 123
+# is the largest H the train launcher admits (4H <= 1024 threads AND
+# 8*H*H <= 120 KB of Wh).
+@pytest.mark.parametrize("H", [64, 123])
+def test_lstm_seq_train_parity_hidden_sizes(ext, H):
+    _check_lstm_seq_train(1, H, 2)
+
+
+def _lstm_seq_reference(xg, wh, h0, c0, done):
+    """fp32 torch loop on the same bf16 inputs; forget bias 1.0."""
+    h, c = h0, c0
+    outs = []
+    for t in range(xg.shape[1]):
+        gates = xg[:, t].float() + h.float() @ wh.float()
+        i, gg, f, o = gates.chunk(4, dim=1)
+        c_new = torch.sigmoid(f + 1.0) * c + torch.sigmoid(i) * torch.tanh(gg)
+        h_new = torch.sigmoid(o) * torch.tanh(c_new)
+        outs.append(h_new)
+        keep = (~done[:, t]).float().unsqueeze(1)
+        h, c = h_new * keep, c_new * keep
+    return torch.stack(outs, dim=1), h, c
+
+
+@pytest.mark.parametrize("H", [64, 140, 256])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_lstm_seq_fwd_hidden_sizes(ext, H, dtype):
+    """drla_lstm_seq_fwd called directly at the smallest hidden size the
+    tests use and at the largest its block-size cap (4H <= 1024) admits,
+    B = 1, L = 2, against the torch loop at test_lstm_seq_train_parity's
+    forward tolerances.
+
+    Wh stays in LDS while it fits: H = 140 is the largest such size
+    (156816 dynamic + 4096 static of 163840 bytes). H = 256 would need
+    530448 bytes, so there the launcher picks drla_lstm_seq_fwd_gmem, the
+    same body with Wh read from global memory and only the carries in
+    LDS."""
+    torch.manual_seed(31 + H)
+    B, L = 1, 2
+    xg = (torch.randn(B, L, 4 * H, device="cuda") * 0.5).to(dtype)
+    wh = (torch.randn(H, 4 * H, device="cuda") * 0.2).to(torch.bfloat16)
+    h0 = torch.randn(B, H, device="cuda")
+    c0 = torch.randn(B, H, device="cuda")
+    done = torch.tensor([[True, False]], device="cuda")
+    h_out, h_fin, c_fin = ext.lstm_seq_fwd(xg, wh, h0, c0, done, 1.0)
+    ref, h, c = _lstm_seq_reference(xg, wh, h0, c0, done)
+    assert torch.allclose(h_out, ref, atol=2e-2, rtol=2e-2)
+    assert torch.allclose(h_fin, h, atol=2e-2, rtol=2e-2)
+    assert torch.allclose(c_fin, c, atol=3e-2, rtol=3e-2)
+
+
+def test_lstm_seq_train_refuses_non_bf16_wh(ext):
+    """float32 Wh where bf16 bits are expected (wider, so a missing check
+    could only misread inside the buffer)."""
+    B, L, H = 1, 2, 64
+    xg = torch.zeros(B, L, 4 * H, device="cuda", dtype=torch.bfloat16)
+    Wh = torch.zeros(H, 4 * H, device="cuda")
+    h0 = torch.zeros(B, H, device="cuda")
+    done = torch.zeros(B, L, dtype=torch.bool, device="cuda")
+    with pytest.raises(RuntimeError, match=r"\bWh must be bf16"):
+        ext.lstm_seq_train_fwd(xg, Wh, h0, h0.clone(), done, 1.0)
+
+
+def _check_lstm_seq_train(B, H, L):
     from distributed_reinforcement_learning_amd.ops.lstm_op import (
         lstm_seq_train,
     )
     torch.manual_seed(21)
-    B, H = 5, 64
     xg = (torch.randn(B, L, 4 * H, device="cuda") * 0.5).to(
         torch.bfloat16).requires_grad_(True)
     wh = (torch.randn(H, 4 * H, device="cuda") * 0.2).to(

@@ -29,11 +29,40 @@ def _torch_composed(logits, value, mu, actions, rewards, discounts,
     return pi, bl, ent
 
 
+# trajectory-length cap of the fused kernel (VT_MAX_T in ops/hip/drla_common.h:
+# it sizes the kernel's LDS scan buffers and the launcher's check)
+VT_MAX_T = 128
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_fused_vtrace_loss_matches_torch(dtype):
+    _check_fused_vtrace_loss(dtype, 8, 12, 18)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_fused_vtrace_loss_at_the_trajectory_cap(dtype):
+    """T = VT_MAX_T fills the kernel's LDS scan buffers exactly; one
+    block, two actions."""
+    _check_fused_vtrace_loss(dtype, 1, VT_MAX_T, 2)
+
+
+def test_fused_vtrace_loss_refuses_past_the_trajectory_cap():
+    from distributed_reinforcement_learning_amd.ops import fused_vtrace_loss
+    B, T, A = 1, VT_MAX_T + 1, 2
+    logits = torch.zeros(B, T, A, device="cuda")
+    with pytest.raises(RuntimeError, match=f"trajectory cap is {VT_MAX_T}"):
+        fused_vtrace_loss(
+            logits, torch.zeros(B, T, device="cuda"),
+            torch.full((B, T, A), 0.5, device="cuda"),
+            torch.zeros(B, T, dtype=torch.long, device="cuda"),
+            torch.zeros(B, T, device="cuda"),
+            torch.zeros(B, T, dtype=torch.bool, device="cuda"), 0.99,
+            "abs_one", 0.7, 0.03)
+
+
+def _check_fused_vtrace_loss(dtype, B, T, A):
     from distributed_reinforcement_learning_amd.ops import fused_vtrace_loss
     torch.manual_seed(0)
-    B, T, A = 8, 12, 18
     c_b, c_e = 0.7, 0.03
     logits = (torch.randn(B, T, A, device="cuda") * 2).to(dtype)
     logits_f = logits.detach().clone().requires_grad_(True)
