@@ -532,6 +532,7 @@ void per_update(torch::Tensor tree, torch::Tensor idxs,
   check_all_gpu_contig("per tensor", tree, idxs, prios);
   TORCH_CHECK(idxs.scalar_type() == torch::kLong, "idxs must be i64");
   const int n = idxs.numel();
+  if (n == 0) return;  // a zero-block grid is an invalid launch
   hipLaunchKernelGGL(drla_per_update, dim3((n + 255) / 256), dim3(256), 0,
                      cur_stream(), tree.data_ptr<float>(), i64p(idxs),
                      prios.data_ptr<float>(), n, cap);
@@ -563,6 +564,7 @@ void multi_gather(torch::Tensor rows, torch::Tensor srcs,
   TORCH_CHECK(rows.scalar_type() == torch::kLong, "rows must be i64");
   const int B = rows.numel();
   const int F = srcs.numel();
+  if (B == 0 || F == 0) return;  // a zero-block grid is an invalid launch
   const long long total = (long long)B * max_chunks;
   const int gx = (int)std::min<long long>((total + 255) / 256, 4096);
   hipLaunchKernelGGL(drla_multi_gather, dim3(gx, F), dim3(256), 0,
@@ -580,6 +582,7 @@ std::tuple<torch::Tensor, torch::Tensor> per_sample(torch::Tensor tree,
   const int n = s.numel();
   auto idx = torch::empty({n}, s.options().dtype(torch::kLong));
   auto prio = torch::empty({n}, s.options().dtype(torch::kFloat));
+  if (n == 0) return {idx, prio};  // a zero-block grid is an invalid launch
   hipLaunchKernelGGL(drla_per_sample, dim3((n + 255) / 256), dim3(256), 0,
                      cur_stream(), tree.data_ptr<float>(),
                      s.data_ptr<float>(), n_entries.data_ptr<float>(),

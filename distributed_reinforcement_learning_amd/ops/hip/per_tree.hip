@@ -99,8 +99,11 @@ extern "C" __global__ void drla_per_sample(
   }
   // float32 rounding at a segment boundary can walk past the last
   // WRITTEN leaf onto a zero-priority slot -> stale payload and an
-  // infinite IS weight ((n*0)^-beta); clamp into the populated range
-  const long long last = cap - 2 + (long long)n_entries[0];
+  // infinite IS weight ((n*0)^-beta); clamp into the populated range.
+  // An empty tree clamps to leaf 0 (row 0), like the CPU twin's
+  // max(n_entries, 1) — never to cap-2, an interior node (row -1).
+  const long long ne = (long long)n_entries[0];
+  const long long last = cap - 2 + (ne > 1 ? ne : 1);
   if (idx > last) idx = last;
   out_idx[i] = idx;
   out_prio[i] = tree[idx];

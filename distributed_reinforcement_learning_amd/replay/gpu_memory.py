@@ -33,6 +33,12 @@ class GpuMemory:
                                                               torch.dtype]],
                  device: str = "cuda:0", seed: Optional[int] = None):
         self.capacity = int(capacity)
+        # n_entries travels to drla_per_sample as a float32 device buffer,
+        # exact only below 2^24; refuse before anything is allocated
+        if self.capacity >= 2 ** 24:
+            raise ValueError(
+                f"GpuMemory capacity {self.capacity} >= 2**24: n_entries "
+                "is carried as float32 and would no longer be exact")
         self.device = torch.device(device)
         self.tree = torch.zeros(2 * self.capacity - 1, dtype=torch.float32,
                                 device=self.device)
@@ -65,13 +71,19 @@ class GpuMemory:
         """errors [n] (device); samples name -> [n, ...] device tensors."""
         ext = _ops.require_ext()
         n = errors.numel()
-        rows = (self.write + torch.arange(n, device=self.device)) \
+        # more than one lap of the ring: only the last `capacity` entries
+        # survive (last write wins, like the CPU twin). Duplicate rows in
+        # one indexed store / one drla_per_update are unordered on a GPU,
+        # so drop the overwritten head here; `write` still advances by n.
+        skip = max(n - self.capacity, 0)
+        rows = (self.write + torch.arange(skip, n, device=self.device)) \
             % self.capacity
         for k, buf in self.data.items():
-            buf[rows] = samples[k].to(buf.dtype)
+            buf[rows] = samples[k][skip:].to(buf.dtype)
         idxs = rows + (self.capacity - 1)
         ext.per_update(self.tree, idxs.contiguous(),
-                       self._prio(errors).contiguous(), self.capacity)
+                       self._prio(errors.reshape(-1)[skip:]).contiguous(),
+                       self.capacity)
         self.write = int((self.write + n) % self.capacity)
         self.n_entries = min(self.n_entries + n, self.capacity)
         self.n_entries_buf.fill_(float(self.n_entries))

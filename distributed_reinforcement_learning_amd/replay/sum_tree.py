@@ -71,6 +71,12 @@ class SumTree:
         ps = np.asarray(ps, dtype=np.float64)[keep]
         deltas = ps - self.tree[idxs]
         self.tree[idxs] = ps
+        # capacity 1: the leaf IS the root, nothing above it to update
+        # ((0 - 1) // 2 == -1 would wrap to tree[0] and double the root)
+        above = idxs > 0
+        idxs, deltas = idxs[above], deltas[above]
+        if idxs.size == 0:
+            return
         parents = (idxs - 1) // 2
         while True:
             np.add.at(self.tree, parents, deltas)

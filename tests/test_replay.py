@@ -145,3 +145,73 @@ def test_refresh_master_after_out_of_band_param_rewrite():
     opt.step(lr=0.0)  # lr 0: step must be a no-op on the params
     assert torch.equal(p.detach(), new), \
         "stale master reverted the out-of-band rewrite"
+
+
+# -- PER reference self-check, capacity-1 tree, capacity guard ---------------
+
+
+def _dyadic_tree(cap, fill, seed):
+    from _per_ref import dyadic_priorities
+    rng = np.random.default_rng(seed)
+    t = SumTree(cap)
+    t.add_batch(dyadic_priorities(rng, fill), [None] * fill)
+    return t
+
+
+@pytest.mark.parametrize("cap", [2, 3, 5, 13, 100, 1000])
+@pytest.mark.parametrize("full", [False, True], ids=["partial", "full"])
+def test_descent_f32_matches_sum_tree_on_dyadic_trees(cap, full):
+    """The GPU tests' float32 descent reference agrees with the float64
+    SumTree on every multiple of 1/16 in [0, total] and past the end, at
+    non-power-of-two capacities, partly filled and full."""
+    from _per_ref import descent_f32
+    fill = cap if full else max(cap // 3, 1)
+    t = _dyadic_tree(cap, fill, seed=cap)
+    total = t.total()
+    assert total == t.tree[cap - 1:].sum()  # dyadic: exact
+    assert total * 16 == int(total * 16)
+    s = np.arange(0, int(total * 16) + 1, dtype=np.float64) / 16.0
+    s = np.concatenate([s, [total + 1 / 16, 1.5 * total]])
+    assert np.array_equal(s.astype(np.float32).astype(np.float64), s)
+    want = t.retrieve_batch(s)
+    got = descent_f32(t.tree.astype(np.float32), s.astype(np.float32), cap,
+                      t.n_entries)
+    np.testing.assert_array_equal(got, want)
+    # and both agree with the O(n) definition: the first leaf, in
+    # left-to-right order, whose inclusive prefix sum reaches s, clamped to
+    # the last written leaf. Left to right the deepest level comes first:
+    # leaves [2^d - 1, 2cap - 2], then the shallower [cap - 1, 2^d - 2].
+    deep = (1 << int(np.log2(2 * cap - 1))) - 1
+    order = np.concatenate([np.arange(deep, 2 * cap - 1),
+                            np.arange(cap - 1, deep)])
+    cum = np.cumsum(t.tree[order])
+    pos = np.minimum(np.searchsorted(cum, s, side="left"), cap - 1)
+    naive = np.minimum(order[pos], cap - 2 + fill)
+    np.testing.assert_array_equal(want, naive)
+
+
+def test_sum_tree_capacity_one():
+    t = SumTree(1)
+    t.add(3.5, "a")
+    assert t.total() == 3.5
+    t.update(0, 1.25)
+    assert t.total() == 1.25
+    assert t.tree.tolist() == [1.25]
+    assert int(t.retrieve_batch(np.array([0.5]))[0]) == 0
+
+
+def test_gpu_memory_refuses_capacity_past_float32_exactness(monkeypatch):
+    """n_entries travels as float32: capacities >= 2**24 are refused, and
+    refused before anything is allocated."""
+    import torch
+    from distributed_reinforcement_learning_amd.replay.gpu_memory import (
+        GpuMemory,
+    )
+
+    def _no_alloc(*a, **k):
+        raise AssertionError("allocated before the capacity check")
+
+    monkeypatch.setattr(torch, "zeros", _no_alloc)
+    monkeypatch.setattr(torch, "tensor", _no_alloc)
+    with pytest.raises(ValueError):
+        GpuMemory(2 ** 24, fields={}, device="cpu")
