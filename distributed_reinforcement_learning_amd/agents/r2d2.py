@@ -10,6 +10,12 @@ the hidden state (the R2D2 paper's burn-in), then the trained window unrolls
 with gradient. ``burn_in_gradient=True`` reproduces the reference's exact
 behavior (gradient flows through the burn-in steps; the loss is still sliced
 at burn_in) for parity checks.
+
+Beyond the reference: ``n_step`` > 1 trains on n-step returns under the
+value rescaling, taken inside the post-burn-in window and truncated at its
+end, and ``priority_eta`` switches the sequence priority to the R2D2
+paper's eta*max|TD| + (1-eta)*mean|TD| (algorithms/nstep.py). The defaults
+(1, None) are the reference's 1-step targets and |mean TD|.
 """
 
 from __future__ import annotations
@@ -22,6 +28,7 @@ import torch
 from distributed_reinforcement_learning_amd.agents.base import AgentBase, clip_rewards
 from distributed_reinforcement_learning_amd.algorithms import burn_in as rescale
 from distributed_reinforcement_learning_amd.algorithms import dqn
+from distributed_reinforcement_learning_amd.algorithms import nstep
 from distributed_reinforcement_learning_amd.models import R2D2LstmQ
 from distributed_reinforcement_learning_amd.ops import FusedAdam
 
@@ -34,8 +41,20 @@ class Agent(AgentBase):
                  reward_clipping: str = "abs_one", device: str = "cpu",
                  compute_dtype: torch.dtype = torch.bfloat16,
                  build_optimizer: bool = True, seed: Optional[int] = None,
-                 burn_in_gradient: bool = False):
+                 burn_in_gradient: bool = False, n_step: int = 1,
+                 priority_eta: Optional[float] = None):
         super().__init__(device=device, compute_dtype=compute_dtype)
+        if int(n_step) != n_step or n_step < 1:
+            raise ValueError(f"n_step={n_step!r} must be an integer >= 1")
+        if priority_eta is not None and not 0.0 <= priority_eta <= 1.0:
+            raise ValueError(
+                f"priority_eta={priority_eta!r} must be in [0, 1] or None")
+        # n-step returns inside the post-burn-in window, truncated at its
+        # end (algorithms/nstep.py); priority_eta None keeps the
+        # reference's |mean TD| sequence priority
+        self.n_step = int(n_step)
+        self.priority_eta = (None if priority_eta is None
+                             else float(priority_eta))
         self.seq_len = seq_len
         self.burn_in = burn_in
         self.input_shape = tuple(input_shape)
@@ -170,7 +189,8 @@ class Agent(AgentBase):
     def _fused_seq_loss(self, state, previous_action, action, h0, c0,
                         reward, done, w, with_grad: bool):
         """GPU fast path: one-kernel TD tail (K9, ops/hip/r2d2_loss.hip)
-        over the trained window. Returns (weighted loss, |mean td| [B])."""
+        over the trained window; the n-step kernel when n_step > 1 or
+        priority_eta is set. Returns (weighted loss, priorities [B])."""
         from distributed_reinforcement_learning_amd.ops.r2d2_op import (
             fused_r2d2_loss,
         )
@@ -180,7 +200,8 @@ class Agent(AgentBase):
         b = self.burn_in
         return fused_r2d2_loss(main_w, tgt_w, a[:, b:], r[:, b:],
                                d[:, b:], w, self.discount_factor,
-                               self.reward_clipping)
+                               self.reward_clipping, n_step=self.n_step,
+                               priority_eta=self.priority_eta)
 
     def _sequence_losses(self, state, previous_action, action, h0, c0,
                          reward, done, with_grad: bool):
@@ -209,16 +230,16 @@ class Agent(AgentBase):
         br, bg, ba = clipped_r[:, b:], discounts[:, b:], a[:, b:]
 
         state_main_q = bm[:, :-1]
-        next_main_q = bm[:, 1:]
-        next_target_q = bt[:, 1:]
         act = ba[:, :-1]
-        rew, dis = br[:, :-1], bg[:, :-1]
 
         sav = dqn.take_state_action_value(state_main_q, act)
-        next_action = next_main_q.argmax(dim=2)
-        nsav = dqn.take_state_action_value(next_target_q, next_action)
+        # every row's own double-DQN bootstrap (row 0's is never used);
+        # nstep_window_target picks row t+k for position t
+        own_action = bm.argmax(dim=2)
+        nsav = dqn.take_state_action_value(bt, own_action)
         rescaled_next = rescale.inverse_value_function_rescaling(nsav)
-        rescaled_target = (rescaled_next * dis + rew).detach()
+        rescaled_target = nstep.nstep_window_target(
+            rescaled_next, br, bg, self.n_step).detach()
         target_value = rescale.value_function_rescaling(rescaled_target)
         unweighted = ((target_value - sav) ** 2).mean(dim=1)
         return unweighted, target_value, sav
@@ -229,8 +250,9 @@ class Agent(AgentBase):
     def get_td_error(self, state, previous_action, action, h, c, reward,
                      done) -> float:
         """Priority for ONE freshly-arrived sequence: |mean TD| (reference
-        agent/r2d2.py:97-127). h/c are the per-step stored states; step 0's
-        is the sequence's initial state."""
+        agent/r2d2.py:97-127), or the eta max/mean mix when priority_eta
+        is set. h/c are the per-step stored states; step 0's is the
+        sequence's initial state."""
         h0 = np.asarray(h)[0]
         c0 = np.asarray(c)[0]
         _, target_value, sav = self._sequence_losses(
@@ -238,7 +260,8 @@ class Agent(AgentBase):
             np.asarray(action)[None], h0[None], c0[None],
             np.asarray(reward)[None], np.asarray(done)[None],
             with_grad=False)
-        return float((target_value - sav).mean().abs())
+        return float(nstep.sequence_priority(target_value - sav,
+                                             self.priority_eta)[0])
 
     @torch.no_grad()
     def get_td_error_batch(self, state, previous_action, action, h0, c0,
@@ -255,13 +278,14 @@ class Agent(AgentBase):
         _, target_value, sav = self._sequence_losses(
             state, previous_action, action, h0, c0, reward, done,
             with_grad=False)
-        td = (target_value - sav).mean(dim=1).abs()
+        td = nstep.sequence_priority(target_value - sav, self.priority_eta)
         return td if as_tensor else td.cpu().numpy()
 
     def compute_sequence_loss(self, state, previous_action, action, h0,
                               c0, reward, done, w):
         """Pure loss body (shared by train and the graphed replay step):
-        returns (weighted scalar loss, per-sequence |mean TD| tensor)."""
+        returns (weighted scalar loss, per-sequence priority tensor —
+        |mean TD|, or the priority_eta max/mean mix)."""
         if self._use_fused_tail():
             w_t = self.to_device(w, torch.float32)
             return self._fused_seq_loss(state, previous_action, action,
@@ -271,7 +295,8 @@ class Agent(AgentBase):
             state, previous_action, action, h0, c0, reward, done,
             with_grad=True)
         loss = (unweighted * w).mean()
-        td = (target_value - sav).mean(dim=1).abs().detach()
+        td = nstep.sequence_priority(target_value - sav,
+                                     self.priority_eta).detach()
         return loss, td
 
     def train(self, state, previous_action, action, h, c, reward, done,

@@ -25,6 +25,7 @@ def check_properties(data: Dict[str, Any]) -> None:
     * every per-actor list has length num_actors
     * available_action[i] <= model_output
     * reward_clipping is a known mode
+    * n_step (integer >= 1) and priority_eta (in [0, 1]), if present
     """
     num_actors = data["num_actors"]
     envs = data["env"]
@@ -43,6 +44,16 @@ def check_properties(data: Dict[str, Any]) -> None:
     rc = data.get("reward_clipping", "abs_one")
     if rc not in _VALID_REWARD_CLIPPING:
         raise ValueError(f"unknown reward_clipping {rc!r}")
+    # optional R2D2 keys, checked only when present
+    if "n_step" in data:
+        n = data["n_step"]
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"n_step={n!r} must be an integer >= 1")
+    if "priority_eta" in data:
+        eta = data["priority_eta"]
+        if (isinstance(eta, bool) or not isinstance(eta, (int, float))
+                or not 0.0 <= eta <= 1.0):
+            raise ValueError(f"priority_eta={eta!r} must be in [0, 1]")
 
 
 @dataclass

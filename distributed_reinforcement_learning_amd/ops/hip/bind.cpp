@@ -10,6 +10,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
 #include <tuple>
 
@@ -398,9 +399,12 @@ static int next_pow2(int x) {
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> r2d2_loss_fwd(
     torch::Tensor mq, torch::Tensor tq, torch::Tensor actions,
     torch::Tensor rewards, torch::Tensor done, torch::Tensor weights,
-    double gamma, int64_t clip_mode) {
+    double gamma, int64_t clip_mode, int64_t n_step, double priority_eta) {
   check_all_gpu_contig("r2d2 loss input", mq, tq, actions, rewards, done,
                        weights);
+  TORCH_CHECK(n_step >= 1, "n_step must be >= 1");
+  TORCH_CHECK(priority_eta <= 1.0,
+              "priority_eta must be <= 1 (negative: |mean td| priority)");
   TORCH_CHECK(actions.scalar_type() == torch::kInt, "actions must be i32");
   TORCH_CHECK(done.scalar_type() == torch::kBool, "done must be bool");
   const int B = mq.size(0), W = mq.size(1), A = mq.size(2);
@@ -412,13 +416,25 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> r2d2_loss_fwd(
   auto td_st = torch::empty({B, W - 1}, fopt);
   auto td_out = torch::empty({B}, fopt);
   const int block = next_pow2(W - 1);
+  if (n_step == 1 && priority_eta < 0.0) {
+    hipLaunchKernelGGL(
+        drla_r2d2_loss_fwd, dim3(B), dim3(block), 0, cur_stream(),
+        m.bf16, m.f32, t.bf16, t.f32, actions.data_ptr<int>(),
+        rewards.data_ptr<float>(), boolp(done), weights.data_ptr<float>(),
+        static_cast<float>(gamma), static_cast<int>(clip_mode),
+        loss.data_ptr<float>(), td_st.data_ptr<float>(),
+        td_out.data_ptr<float>(), B, W, A);
+    return {loss, td_st, td_out};
+  }
+  // every n >= W-1 truncates at the window end alike
+  const int n = static_cast<int>(std::min<int64_t>(n_step, W));
   hipLaunchKernelGGL(
-      drla_r2d2_loss_fwd, dim3(B), dim3(block), 0, cur_stream(),
+      drla_r2d2_nstep_loss_fwd, dim3(B), dim3(block), 0, cur_stream(),
       m.bf16, m.f32, t.bf16, t.f32, actions.data_ptr<int>(),
       rewards.data_ptr<float>(), boolp(done), weights.data_ptr<float>(),
-      static_cast<float>(gamma), static_cast<int>(clip_mode),
-      loss.data_ptr<float>(), td_st.data_ptr<float>(),
-      td_out.data_ptr<float>(), B, W, A);
+      static_cast<float>(gamma), static_cast<int>(clip_mode), n,
+      static_cast<float>(priority_eta), loss.data_ptr<float>(),
+      td_st.data_ptr<float>(), td_out.data_ptr<float>(), B, W, A);
   return {loss, td_st, td_out};
 }
 
@@ -1186,7 +1202,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("a2c_loss_fwd", &a2c_loss_fwd, "fused A2C loss fwd (K6)");
   m.def("a2c_loss_bwd", &a2c_loss_bwd, "fused A2C loss bwd (K6)");
   m.def("r2d2_loss_fwd", &r2d2_loss_fwd,
-        "fused R2D2 sequence-TD tail fwd (K9)");
+        "fused R2D2 sequence-TD tail fwd (K9; n_step > 1 or "
+        "priority_eta >= 0 selects the n-step kernel)",
+        py::arg("mq"), py::arg("tq"), py::arg("actions"), py::arg("rewards"),
+        py::arg("done"), py::arg("weights"), py::arg("gamma"),
+        py::arg("clip_mode"), py::arg("n_step") = 1,
+        py::arg("priority_eta") = -1.0);
   m.def("dhead_train_fwd", &dhead_train_fwd,
         "grad-carrying dueling head fwd (R2D2 trained window)");
   m.def("dhead_train_bwd", &dhead_train_bwd,

@@ -140,6 +140,10 @@ DRLA_KERNEL drla_r2d2_loss_fwd(
     const bf16raw*, const float*, const bf16raw*, const float*, const int*,
     const float*, const unsigned char*, const float*, float, int, float*,
     float*, float*, int, int, int);
+DRLA_KERNEL drla_r2d2_nstep_loss_fwd(
+    const bf16raw*, const float*, const bf16raw*, const float*, const int*,
+    const float*, const unsigned char*, const float*, float, int, int, float,
+    float*, float*, float*, int, int, int);
 DRLA_KERNEL drla_r2d2_loss_bwd(const float*, const int*, const float*,
                                const float*, bf16raw*, float*, int, int,
                                int);

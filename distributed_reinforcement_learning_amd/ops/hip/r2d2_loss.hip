@@ -108,6 +108,100 @@ extern "C" __global__ void drla_r2d2_loss_fwd(
   }
 }
 
+// n-step form of the K9 forward (R2D2 paper: 5-step returns under h, and
+// eta*max|td| + (1-eta)*mean|td| sequence priorities). Per (b, t<W-1), all
+// rows inside the post-burn-in window:
+//   k      = min(n, W-1-t)                 (truncate at the window end)
+//   Gam_0  = 1, Gam_{j+1} = Gam_j * disc_{t+j},  disc_u = done_u ? 0 : gamma
+//   G      = sum_{j<k} Gam_j * clip(r_{t+j})
+//   a*     = argmax_a Qm[b,t+k,a]
+//   td     = h( G + Gam_k * h^-1(Qt[b,t+k,a*]) ) - Qm[b,t,act_t]
+// so a done at t+j zeroes every later reward and the bootstrap. At n = 1
+// this is drla_r2d2_loss_fwd's math; td_st keeps its [B,W-1] layout, so
+// drla_r2d2_loss_bwd serves both.
+//
+// One block per sequence. Phase 1 strides over all W rows (blockDim need
+// not reach W): clip(r_u), disc_u and the row's own bootstrap
+// h^-1(Qt[u, a*_u]) go to LDS, so every argmax/h^-1 is evaluated once
+// however many t's bootstrap from it. Phase 2: lane t accumulates at most n
+// steps from LDS, stopping once Gam hits 0. blockDim is a power of two
+// >= W-1 (the tree reduce needs it). eta < 0 selects the legacy |mean td|
+// priority.
+extern "C" __global__ void drla_r2d2_nstep_loss_fwd(
+    const bf16raw* __restrict__ mq16, const float* __restrict__ mq32,
+    const bf16raw* __restrict__ tq16, const float* __restrict__ tq32,
+    const int* __restrict__ actions,     // [B,W]
+    const float* __restrict__ rewards,   // [B,W] raw
+    const unsigned char* __restrict__ done,  // [B,W]
+    const float* __restrict__ weights,   // [B]
+    float gamma, int clip_mode, int n_step, float eta,
+    float* __restrict__ loss,    // [1], zeroed by caller
+    float* __restrict__ td_st,   // [B,W-1] signed td stash (backward)
+    float* __restrict__ td_out,  // [B] priorities
+    int B, int W, int A) {
+  const int b = blockIdx.x;
+  const int t = threadIdx.x;
+  const int T1 = W - 1;
+  __shared__ float s_r[1024];     // clip(r_u)
+  __shared__ float s_d[1024];     // disc_u
+  __shared__ float s_boot[1024];  // h^-1(Qt[u, a*_u]), u >= 1
+  __shared__ float sq[1024];
+  __shared__ float sm[1024];
+  __shared__ float sa[1024];
+  __shared__ float sx[1024];
+  for (int u = t; u < W; u += blockDim.x) {
+    const long long bu = (long long)b * W + u;
+    s_r[u] = r2_clip(rewards[bu], clip_mode);
+    s_d[u] = done[bu] ? 0.0f : gamma;
+    if (u > 0) {
+      const long long row = bu * A;
+      int astar = 0;
+      float best = r2_ld(mq16, mq32, row);
+      for (int a = 1; a < A; ++a) {
+        const float v = r2_ld(mq16, mq32, row + a);
+        if (v > best) { best = v; astar = a; }
+      }
+      s_boot[u] = r2_hinv(r2_ld(tq16, tq32, row + astar));
+    }
+  }
+  __syncthreads();
+  float td = 0.0f;
+  if (t < T1) {
+    const int k = min(n_step, T1 - t);
+    float g = 0.0f, gam = 1.0f;
+    for (int j = 0; j < k && gam != 0.0f; ++j) {
+      g += gam * s_r[t + j];
+      gam *= s_d[t + j];
+    }
+    const float z = gam != 0.0f ? g + gam * s_boot[t + k] : g;
+    const long long bt = (long long)b * W + t;
+    const float sav = r2_ld(mq16, mq32,
+                            bt * A + drla_clamp_idx(actions[bt], A));
+    td = r2_h(z) - sav;
+    td_st[(long long)b * T1 + t] = td;
+  }
+  const float atd = fabsf(td);
+  sq[t] = td * td;
+  sm[t] = td;
+  sa[t] = atd;
+  sx[t] = atd;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      sq[t] += sq[t + s];
+      sm[t] += sm[t + s];
+      sa[t] += sa[t + s];
+      sx[t] = fmaxf(sx[t], sx[t + s]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    atomicAdd(loss, weights[b] * sq[0] / T1 / B);
+    td_out[b] = eta < 0.0f ? fabsf(sm[0] / T1)
+                           : eta * sx[0] + (1.0f - eta) * (sa[0] / T1);
+  }
+}
+
 // No-grad dueling head over the post-burn-in window, ONE launch:
 //   x = relu(h @ Wt^T + bt);  y = x @ Wo^T + bo;  q = y[:A] - y[A]
 // replacing the 5-kernel torch chain (cast, trunk addmm, relu, out addmm,

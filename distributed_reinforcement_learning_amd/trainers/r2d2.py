@@ -45,7 +45,9 @@ def build_agent(ctx, device: str, build_optimizer: bool, seed=None):
         learning_frame=cfg.learning_frame,
         gradient_clip_norm=cfg.gradient_clip_norm,
         reward_clipping=cfg.reward_clipping, device=device,
-        build_optimizer=build_optimizer, seed=seed)
+        build_optimizer=build_optimizer, seed=seed,
+        # optional keys, like envs_per_actor: absent = reference behaviour
+        n_step=cfg.get("n_step", 1), priority_eta=cfg.get("priority_eta"))
 
 
 def learner(ctx: common.TrainerContext, supervisor=None) -> None:

@@ -94,7 +94,7 @@ def bench_apex(steps=200, warmup=30):
         "batch": cfg.batch_size}), flush=True)
 
 
-def bench_r2d2(steps=200, warmup=30):
+def bench_r2d2(steps=200, warmup=30, n_step=1, priority_eta=None):
     from distributed_reinforcement_learning_amd.agents import r2d2 as r2d2_agent
     cfg = load_config("config.json", "r2d2")
     dev = "cuda:0"
@@ -107,7 +107,8 @@ def bench_r2d2(steps=200, warmup=30):
         learning_frame=cfg.learning_frame,
         gradient_clip_norm=cfg.gradient_clip_norm,
         reward_clipping=cfg.reward_clipping, device=dev,
-        build_optimizer=True, seed=3)
+        build_optimizer=True, seed=3, n_step=n_step,
+        priority_eta=priority_eta)
     H, W, C = cfg.model_input
     L = cfg.seq_len
     mem = GpuMemory(100_000, fields={
@@ -168,7 +169,8 @@ def bench_r2d2(steps=200, warmup=30):
         "algo": "r2d2", "ms_per_train_step": dt * 1000,
         "train_steps_per_s": 1 / dt,
         "sequences_per_s": cfg.batch_size / dt,
-        "batch": cfg.batch_size, "seq_len": L, "burn_in": cfg.burn_in}),
+        "batch": cfg.batch_size, "seq_len": L, "burn_in": cfg.burn_in,
+        "n_step": n_step, "priority_eta": priority_eta}),
         flush=True)
 
 
