@@ -216,6 +216,12 @@ class _FlatOptimizerBase:
     def step(self, lr: Optional[float] = None) -> None:
         raise NotImplementedError
 
+    def lr_t_for(self, lr: float, t: int) -> float:
+        """What step_tensor_lr expects in lr_buf for update number ``t``
+        (1-based) at scheduled rate ``lr``: the rate itself, unless the
+        update rule folds a step-dependent factor into it (Adam)."""
+        return lr
+
     def step_tensor_lr(self, lr_buf: torch.Tensor) -> None:
         """GPU-only, hipGraph-capturable update: lr is read from a 1-element
         device buffer the host rewrites before each replay."""

@@ -31,25 +31,30 @@ Step structure (three graphs + a copy stream):
   host:     record consume-event; losses stay on-device until
             last_losses()
 
-Weights and optimizer state are snapshotted before the warmup iterations and
-restored before capture, so graphing never perturbs training state.
+The eager warmup, its snapshot/restore of training state and the capture of
+graph 3 are shared with the other learners: runtime/_capture.py.
 """
 
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
+from distributed_reinforcement_learning_amd.ops import conv_op
+from distributed_reinforcement_learning_amd.runtime._capture import (
+    CapturedStep, OptimizerGraph, warmup_preserving_state,
+)
 
-class GraphedImpalaStep:
+
+class GraphedImpalaStep(CapturedStep):
     def __init__(self, agent, batch_size: int, warmup_iters: int = 3):
         assert agent.device.type == "cuda", "graphed step needs a GPU"
         # u8 conv layers stash their input in-kernel from here on: the
         # overlapped H2D rewrites the static input buffers during the
         # backward, and the l1 wgrad re-reads the input (see _fwd)
-        from distributed_reinforcement_learning_amd.ops import conv_op
         conv_op.STASH_INPUTS = True
         self.agent = agent
         B, T = batch_size, agent.trajectory
@@ -85,29 +90,10 @@ class GraphedImpalaStep:
         self._fwd_done = torch.cuda.Event()
         self._copy_stream = torch.cuda.Stream()
         self._primed = False
+        self._last_lr = 0.0
 
-        # ---- warmup (eager, side stream), with state snapshot/restore -----
         opt = agent.optimizer
-        # scatter-grad mode: backward ASSIGNS grads (no per-param
-        # AccumulateGrad adds); one gather kernel packs them (optim.py)
-        opt.enable_scatter_grads()
-        snap_params = opt.flat_params.detach().clone()
-        snap_state = {k: v.detach().clone()
-                      for k, v in opt._state_tensors().items()}
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup_iters):
-                self._fwd_bwd()
-                opt.gather_grads_eager()
-                opt.step_tensor_lr(self.lr_buf)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        with torch.no_grad():
-            opt.flat_params.copy_(snap_params)
-            for k, v in opt._state_tensors().items():
-                v.copy_(snap_state[k])
-            opt.flat_grads.zero_()
+        warmup_preserving_state(opt, self._fwd_bwd, warmup_iters, self.lr_buf)
 
         # ---- capture ------------------------------------------------------
         # forward and backward are SEPARATE graphs so the next step's H2D
@@ -130,48 +116,10 @@ class GraphedImpalaStep:
                                  retain_graph=True)
             # join the side-stream conv wgrads (ops/conv_op.py) so the
             # capture region ends with a single ordered stream
-            from distributed_reinforcement_learning_amd.ops.conv_op import (
-                join_wgrad_stream,
-            )
-            join_wgrad_stream()
+            conv_op.join_wgrad_stream()
         # .grad now holds capture-pool tensors at replay-stable addresses
         opt.build_gather_table()
-        from distributed_reinforcement_learning_amd.parallel.dist import (
-            is_distributed, world_size,
-        )
-        import os as _os
-        self._distributed = is_distributed() and (
-            world_size() > 1 or bool(_os.environ.get("DRLA_FORCE_DIST_GRAPH")))
-        self._eager_reduce = False
-        self.g_opt = torch.cuda.CUDAGraph()
-        if self._distributed:
-            # capture gather + RCCL all-reduce + update as ONE graph
-            # (NCCL/RCCL collectives are capture-legal and every rank
-            # replays in lockstep). Capture failure is FATAL by default —
-            # a silent per-rank eager fallback deadlocks the lockstep
-            # replay (parallel/dist.py handle_capture_failure).
-            try:
-                # prime the communicator outside capture
-                agent.reduce_gradients()
-                torch.cuda.synchronize()
-                with torch.cuda.graph(self.g_opt, pool=self.g_fwd.pool()):
-                    opt.gather_grads()
-                    agent.reduce_gradients()
-                    opt.step_tensor_lr(self.lr_buf)
-            except Exception as exc:
-                from distributed_reinforcement_learning_amd.parallel.dist import (
-                    handle_capture_failure,
-                )
-                handle_capture_failure(exc)
-                self._eager_reduce = True
-                self.g_opt = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_opt, pool=self.g_fwd.pool()):
-                    opt.step_tensor_lr(self.lr_buf)
-        else:
-            with torch.cuda.graph(self.g_opt, pool=self.g_fwd.pool()):
-                # single-GPU: the gather rides inside the optimizer graph
-                opt.gather_grads()
-                opt.step_tensor_lr(self.lr_buf)
+        self._opt = OptimizerGraph(agent, self.lr_buf, self.g_fwd.pool())
 
     def _fwd(self):
         agent = self.agent
@@ -185,8 +133,7 @@ class GraphedImpalaStep:
         # (state is NOT cloned: the conv-l1 forward kernel bundles a
         # pass-through stash of its input instead — ops/conv_op.py
         # STASH_INPUTS, ~4 us bundled vs ~20 us standalone clone)
-        import os as _os
-        if _os.environ.get("DRLA_NO_INPUT_CLONE") != "1":  # measurement-only escape
+        if os.environ.get("DRLA_NO_INPUT_CLONE") != "1":  # measurement-only escape
             for k in ("previous_action", "action", "initial_c"):
                 i[k] = i[k].clone()
         s = agent.prepare_frames(i["state"])
@@ -268,8 +215,7 @@ class GraphedImpalaStep:
                 self.upload_inputs(src)
                 src = None
         main.wait_event(self._uploaded)
-        lr = agent.lr_at(agent.global_step)
-        self.lr_buf.fill_(lr)
+        self._last_lr = self._opt.begin_step()
         self.g_fwd.replay()
         self._fwd_done.record(main)
         if src is not None:
@@ -277,19 +223,14 @@ class GraphedImpalaStep:
             # consumed the PREVIOUS call's upload (one-batch pipeline)
             self._upload_overlapped(src)
         self.g_bwd.replay()
-        if self._distributed and self._eager_reduce:
-            agent.optimizer.gather_grads()
-            agent.reduce_gradients()
-        self.g_opt.replay()
+        self._opt.replay()
         self._consumed.record()
-        agent.optimizer.step_count += 1
         agent.global_step += 1
         agent.num_env_frames += int(np.prod(self.inputs["reward"].shape))
-        self._last_lr = lr
         return self.losses
 
     def last_losses(self) -> Tuple[float, float, float, float]:
         """(pi_loss, baseline_loss, entropy, lr) of the most recent completed
         step — syncs the device."""
         pi, bl, ent = (float(x) for x in self.losses)
-        return pi, bl, ent, getattr(self, "_last_lr", 0.0)
+        return pi, bl, ent, self._last_lr

@@ -4,6 +4,10 @@ import numpy as np
 import pytest
 import torch
 
+from _capture_checks import (
+    assert_after_steps, assert_construction_preserved, snapshot,
+)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,10 +43,12 @@ def test_graphed_step_matches_eager():
     a_graph.model.load_state_dict(a_eager.model.state_dict())
     a_graph.optimizer.flat_params.copy_(a_eager.optimizer.flat_params)
 
+    snap = snapshot(a_graph)
     graphed = GraphedImpalaStep(a_graph, batch_size=4)
     # graph construction must not have perturbed weights
     assert torch.equal(a_graph.optimizer.flat_params,
                        a_eager.optimizer.flat_params)
+    assert_construction_preserved(a_graph, graphed.lr_buf, snap)
 
     for i in range(3):
         b = _batch(seed=i)
@@ -58,6 +64,7 @@ def test_graphed_step_matches_eager():
         # resulting weights must agree closely
         assert out_g[0] == pytest.approx(out_e[0], rel=5e-2, abs=5e-1)
         assert out_g[3] == out_e[3]  # identical lr schedule
+    assert_after_steps(a_graph, graphed.lr_buf, 3)
     assert torch.allclose(a_graph.optimizer.flat_params,
                           a_eager.optimizer.flat_params, atol=1e-2)
 
@@ -114,11 +121,14 @@ def test_graphed_a3c_train_step():
         return pi, bl, ent, total
 
     p_before = agent.optimizer.flat_params.detach().clone()
+    snap = snapshot(agent)
     g = GraphedTrainStep(agent, mk(), loss_fn)
     assert torch.equal(agent.optimizer.flat_params, p_before)
+    assert_construction_preserved(agent, g.lr_buf, snap)
     for _ in range(4):
         out = g.step(mk())
         assert len(out) == 4
-    torch.cuda.synchronize()
+    # the returned lr is the schedule's, not the optimizer's corrected lr_t
+    assert out[3] == assert_after_steps(agent, g.lr_buf, 4)
     assert all(np.isfinite(float(x)) for x in out[:3])
     assert not torch.equal(agent.optimizer.flat_params, p_before)

@@ -4,6 +4,10 @@ import numpy as np
 import pytest
 import torch
 
+from _capture_checks import (
+    assert_after_steps, assert_construction_preserved, snapshot,
+)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -172,11 +176,14 @@ def test_graphed_replay_step_trains():
 
     p_before = agent.optimizer.flat_params.detach().clone()
     tree_before = float(mem.tree[0])
+    snap = snapshot(agent, mem)
     g = GraphedReplayStep(agent, mem, 16, loss_fn)
     # construction must not perturb weights or priorities (snapshot/restore)
     assert torch.equal(agent.optimizer.flat_params, p_before)
     assert float(mem.tree[0]) == pytest.approx(tree_before, rel=1e-4)
+    assert_construction_preserved(agent, g.lr_buf, snap, mem)
     losses = [float(g.step()) for _ in range(5)]
+    assert_after_steps(agent, g.lr_buf, 5)
     assert all(np.isfinite(losses))
     assert not torch.equal(agent.optimizer.flat_params, p_before)
     assert float(mem.tree[0]) != pytest.approx(tree_before, rel=1e-6)
