@@ -18,6 +18,21 @@ import torch.nn.functional as F
 from distributed_reinforcement_learning_amd.models.blocks import (
     ActionEmbedding, AtariConvStack, LSTMCellTF,
 )
+from distributed_reinforcement_learning_amd.ops.lstm_op import (
+    LSTM_SEQ_MAX_HIDDEN,
+)
+
+# widest LSTM output the one-launch dueling head stages in LDS
+# (ops/hip/drla_common.h DHEAD_MAX_IN)
+_DHEAD_MAX_IN = 256
+
+
+def seq_kernels_ok(is_cuda: bool, weight_dtype: torch.dtype,
+                   lstm_size: int) -> bool:
+    """Whether the unroll runs on the LSTM sequence kernels (bf16 weights on
+    the GPU, hidden size within their cap) or on the per-step torch loop."""
+    return (is_cuda and weight_dtype == torch.bfloat16
+            and 1 <= lstm_size <= LSTM_SEQ_MAX_HIDDEN)
 
 
 class R2D2LstmQ(nn.Module):
@@ -79,8 +94,8 @@ class R2D2LstmQ(nn.Module):
             seq_prev_action.reshape(B * L),
         ).reshape(B, L, -1)
 
-        kern_ok = (feat.is_cuda and self.lstm.weight.dtype == torch.bfloat16
-                   and 4 * self.lstm_size <= 1024)
+        kern_ok = seq_kernels_ok(feat.is_cuda, self.lstm.weight.dtype,
+                                 self.lstm_size)
         if kern_ok and not torch.is_grad_enabled():
             from distributed_reinforcement_learning_amd import ops as _o
             ext = _o.require_ext()
@@ -148,8 +163,8 @@ class R2D2LstmQ(nn.Module):
         feat = self.features(
             seq_state.reshape(B * L, *seq_state.shape[2:]),
             seq_prev_action.reshape(B * L)).reshape(B, L, -1)
-        if (feat.is_cuda and self.lstm.weight.dtype == torch.bfloat16
-                and 4 * self.lstm_size <= 1024):
+        if seq_kernels_ok(feat.is_cuda, self.lstm.weight.dtype,
+                          self.lstm_size):
             from distributed_reinforcement_learning_amd import ops as _o
             ext = _o.require_ext()
             F_ = feat.shape[-1]
@@ -160,7 +175,8 @@ class R2D2LstmQ(nn.Module):
                 h0.float().contiguous(), c0.float().contiguous(),
                 seq_done.contiguous(), self.lstm.forget_bias)
             if (self.out.weight.dtype == torch.bfloat16
-                    and self.trunk.weight.dtype == torch.bfloat16):
+                    and self.trunk.weight.dtype == torch.bfloat16
+                    and self.lstm_size <= _DHEAD_MAX_IN):
                 # whole dueling head in one launch (window slice resolved
                 # by index math in-kernel; replaces cast/addmm/relu/addmm/
                 # slice-sub)
@@ -194,8 +210,8 @@ class R2D2LstmQ(nn.Module):
         feat = self.features(
             seq_state.reshape(B * L, *seq_state.shape[2:]),
             seq_prev_action.reshape(B * L)).reshape(B, L, -1)
-        if (feat.is_cuda and self.lstm.weight.dtype == torch.bfloat16
-                and 4 * self.lstm_size <= 1024):
+        if seq_kernels_ok(feat.is_cuda, self.lstm.weight.dtype,
+                          self.lstm_size):
             from distributed_reinforcement_learning_amd import ops as _o
             ext = _o.require_ext()
             F = feat.shape[-1]

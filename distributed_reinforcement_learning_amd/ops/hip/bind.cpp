@@ -944,19 +944,21 @@ std::vector<torch::Tensor> mlp_heads_wgrad(
           db1p, db2p, db3p, db1v, db2v, db3v};
 }
 
-// ---- LSTM sequence kernels (blockDim = 4H, Wh resident in LDS) ------------
-void check_lstm_seq_hidden(int H) {  // one thread per gate
-  TORCH_CHECK(4 * H <= LSTM_SEQ_MAX_GATES, "lstm hidden cap is ",
-              LSTM_SEQ_MAX_GATES / 4);
+// ---- LSTM sequence kernels ------------------------------------------------
+// Sizes the one-thread-per-gate kernels take keep them (no-grad: 4H <= 1024;
+// train pair: Wh resident in LDS, H <= 123); every other size up to
+// LSTM_SEQ_MAX_HIDDEN runs the wide family, which streams Wh from global
+// memory.
+void check_lstm_seq_hidden(int H, const torch::Tensor& Wh) {
+  TORCH_CHECK(H >= 1 && H <= LSTM_SEQ_MAX_HIDDEN, "lstm hidden cap is ",
+              LSTM_SEQ_MAX_HIDDEN, ", got H=", H);
+  TORCH_CHECK(Wh.numel() == (int64_t)drla_lstm_seq_wh_elems(H),
+              "Wh must be [H, 4H] for H=", H);
 }
-
-// dynamic LDS bytes of the train kernels, which have no global-memory
-// variant: Wh + carries + the gate buffer must fit one workgroup's LDS
-int lstm_seq_train_lds(int H) {
-  check_lstm_seq_hidden(H);
-  TORCH_CHECK(drla_lstm_seq_wh_fits_lds(H), "lstm seq-train kernels keep ",
-              "Wh in LDS: H=", H, " does not fit ", DRLA_LDS_BUDGET, " bytes");
-  return drla_lstm_seq_lds_bytes(H);
+// the wide kernels read Wh as pairs of bf16
+void check_lstm_seq_wide_wh(const torch::Tensor& Wh) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(Wh.data_ptr()) % 4 == 0,
+              "lstm wide kernels need a 4-byte aligned Wh");
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_seq_fwd(
@@ -966,7 +968,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_seq_fwd(
   TORCH_CHECK(done.scalar_type() == torch::kBool, "done must be bool");
   const int B = xgates.size(0), L = xgates.size(1);
   const int H = xgates.size(2) / 4;
-  check_lstm_seq_hidden(H);
+  check_lstm_seq_hidden(H, Wh);
   // a Wh too large for LDS is read from global memory instead
   const bool wh_in_lds = drla_lstm_seq_wh_fits_lds(H);
   const DualPtr xg = dual_ptr(xgates);
@@ -974,6 +976,16 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_seq_fwd(
   auto h_out = torch::empty({B, L, H}, fopt);
   auto h_fin = torch::empty({B, H}, fopt);
   auto c_fin = torch::empty({B, H}, fopt);
+  if (4 * H > LSTM_SEQ_MAX_GATES) {  // more gates than one block has threads
+    check_lstm_seq_wide_wh(Wh);
+    hipLaunchKernelGGL(
+        drla_lstm_seq_wide_fwd, dim3(B), dim3(LSTM_SEQ_WIDE_BLOCK),
+        drla_lstm_seq_wide_lds_bytes(H), cur_stream(), xg.bf16, xg.f32,
+        BF16P(Wh), h0.data_ptr<float>(), c0.data_ptr<float>(), boolp(done),
+        h_out.data_ptr<float>(), h_fin.data_ptr<float>(),
+        c_fin.data_ptr<float>(), static_cast<float>(forget_bias), B, L, H);
+    return {h_out, h_fin, c_fin};
+  }
   hipLaunchKernelGGL(
       wh_in_lds ? drla_lstm_seq_fwd : drla_lstm_seq_fwd_gmem, dim3(B),
       dim3(4 * H), drla_lstm_seq_lds_bytes(H, wh_in_lds), cur_stream(),
@@ -1014,9 +1026,9 @@ std::vector<torch::Tensor> lstm_seq_train_fwd(
     torch::Tensor done, double forget_bias) {
   check_all_gpu_contig("lstm_seq_train input", xg, Wh, h0, c0, done);
   const int B = xg.size(0), L = xg.size(1), H = xg.size(2) / 4;
-  const int lds = lstm_seq_train_lds(H);
-  TORCH_CHECK(drla_lstm_seq_wh_elems(H) * sizeof(bf16raw) <= 120 * 1024,
-              "lstm seq-train cap: Wh must fit 120 KB of LDS");
+  check_lstm_seq_hidden(H, Wh);
+  const bool wide = !drla_lstm_seq_train_in_lds(H);
+  if (wide) check_lstm_seq_wide_wh(Wh);
   auto fopt = h0.options().dtype(torch::kFloat);
   auto h_out = torch::empty({B, L, H}, fopt);
   auto h_fin = torch::empty({B, H}, fopt);
@@ -1024,7 +1036,11 @@ std::vector<torch::Tensor> lstm_seq_train_fwd(
   auto acts = torch::empty({B, L, 4 * H}, fopt);
   auto c_prev = torch::empty({B, L, H}, fopt);
   auto h_prev = torch::empty({B, L, H}, xg.options());
-  hipLaunchKernelGGL(drla_lstm_seq_train_fwd, dim3(B), dim3(4 * H), lds,
+  hipLaunchKernelGGL(wide ? drla_lstm_seq_wide_train_fwd
+                          : drla_lstm_seq_train_fwd,
+                     dim3(B), dim3(wide ? LSTM_SEQ_WIDE_BLOCK : 4 * H),
+                     wide ? drla_lstm_seq_wide_lds_bytes(H)
+                          : drla_lstm_seq_lds_bytes(H),
                      cur_stream(), BF16P(xg), BF16P(Wh),
                      h0.data_ptr<float>(), c0.data_ptr<float>(), boolp(done),
                      h_out.data_ptr<float>(), h_fin.data_ptr<float>(),
@@ -1041,13 +1057,18 @@ std::vector<torch::Tensor> lstm_seq_train_bwd(
   check_all_gpu_contig("lstm_seq_train bwd input", dh_out, acts, c_prev, Wh,
                        done);
   const int B = acts.size(0), L = acts.size(1), H = acts.size(2) / 4;
+  check_lstm_seq_hidden(H, Wh);
+  const bool wide = !drla_lstm_seq_train_in_lds(H);
+  if (wide) check_lstm_seq_wide_wh(Wh);
   auto fopt = dh_out.options().dtype(torch::kFloat);
   auto dxg = torch::empty({B, L, 4 * H},
                           dh_out.options().dtype(torch::kBFloat16));
   auto dh0 = torch::empty({B, H}, fopt);
   auto dc0 = torch::empty({B, H}, fopt);
   hipLaunchKernelGGL(
-      drla_lstm_seq_train_bwd, dim3(B), dim3(4 * H), lstm_seq_train_lds(H),
+      wide ? drla_lstm_seq_wide_train_bwd : drla_lstm_seq_train_bwd, dim3(B),
+      dim3(wide ? LSTM_SEQ_WIDE_BLOCK : 4 * H),
+      wide ? drla_lstm_seq_wide_lds_bytes(H) : drla_lstm_seq_lds_bytes(H),
       cur_stream(), dh_out.data_ptr<float>(),
       dh_fin.has_value() ? dh_fin->data_ptr<float>() : nullptr,
       dc_fin.has_value() ? dc_fin->data_ptr<float>() : nullptr,

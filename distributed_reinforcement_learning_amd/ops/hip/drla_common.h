@@ -80,6 +80,26 @@ constexpr bool drla_lstm_seq_wh_fits_lds(int H) {
          DRLA_LDS_BUDGET;
 }
 
+// wide family (drla_lstm_seq_wide_*): fixed block, every thread strides over
+// the gate columns, Wh streamed from global memory; dynamic LDS = f32 gate
+// (backward: gate-grad) buffer [4H], then two f32 [H] carries
+#define LSTM_SEQ_MAX_HIDDEN 512
+#define LSTM_SEQ_WIDE_BLOCK 1024
+constexpr int drla_lstm_seq_wide_lds_bytes(int H) {
+  return (4 * H + 2 * H) * (int)sizeof(float);
+}
+static_assert(drla_lstm_seq_wide_lds_bytes(LSTM_SEQ_MAX_HIDDEN) <= 16 * 1024,
+              "wide LSTM kernels keep only gates and carries in LDS");
+// the LDS-resident train pair takes a size iff its block, Wh and the 120 KB
+// Wh cap all fit (H <= 123); every other size goes to the wide pair
+constexpr bool drla_lstm_seq_train_in_lds(int H) {
+  return 4 * H <= LSTM_SEQ_MAX_GATES && drla_lstm_seq_wh_fits_lds(H) &&
+         drla_lstm_seq_wh_elems(H) * (int)sizeof(bf16raw) <= 120 * 1024;
+}
+static_assert(drla_lstm_seq_train_in_lds(123) &&
+                  !drla_lstm_seq_train_in_lds(124),
+              "train-pair dispatch boundary");
+
 // cap grids at ~8 blocks/CU x 256 CUs and grid-stride the rest
 #define DRLA_MAX_BLOCKS 2048
 

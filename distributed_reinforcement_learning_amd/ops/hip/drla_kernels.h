@@ -64,6 +64,17 @@ DRLA_KERNEL drla_lstm_seq_train_bwd(
     const float*, const float*, const float*, const float*, const float*,
     const bf16raw*, const unsigned char*, bf16raw*, float*, float*, int, int,
     int);
+DRLA_KERNEL drla_lstm_seq_wide_fwd(
+    const bf16raw*, const float*, const bf16raw*, const float*, const float*,
+    const unsigned char*, float*, float*, float*, float, int, int, int);
+DRLA_KERNEL drla_lstm_seq_wide_train_fwd(
+    const bf16raw*, const bf16raw*, const float*, const float*,
+    const unsigned char*, float*, float*, float*, float*, float*, bf16raw*,
+    float, int, int, int);
+DRLA_KERNEL drla_lstm_seq_wide_train_bwd(
+    const float*, const float*, const float*, const float*, const float*,
+    const bf16raw*, const unsigned char*, bf16raw*, float*, float*, int, int,
+    int);
 
 // ---- optim.hip ------------------------------------------------------------
 DRLA_KERNEL drla_sq_norm(const float*, float*, long long);

@@ -387,3 +387,210 @@ extern "C" __global__ void drla_lstm_seq_train_bwd(
     dc0[(long long)b * H + j] = dcc[j];
   }
 }
+
+// ---------------------------------------------------------------------------
+// Wide family: hidden sizes the kernels above cannot take (train H > 123,
+// no-grad H > 256), up to LSTM_SEQ_MAX_HIDDEN. The block size is fixed
+// (LSTM_SEQ_WIDE_BLOCK) and every thread strides over the 4H gate columns,
+// two adjacent columns at a time: one 32-bit load brings both bf16 weights
+// (4H is even and the launcher checks Wh's alignment), which measured 1.82
+// -> 1.40 ms per R2D2 step at H = 512 against one column per load. Wh stays
+// in global memory and is streamed every step — all B workgroups read the
+// same <= 2 MiB, so it is L2 traffic. LDS holds only the gate buffer and the
+// two carries (drla_lstm_seq_wide_lds_bytes). Same math as above: per column
+// f32 accumulation over k = 0..H-1 in order, x-projection added last, done
+// mask on the carry only.
+// ---------------------------------------------------------------------------
+
+template <bool STASH>
+__device__ __forceinline__ void lstm_seq_wide_fwd_impl(
+    const bf16raw* __restrict__ xg16,  // [B,L,4H] (nullable)
+    const float* __restrict__ xg32,      // [B,L,4H] (nullable)
+    const bf16raw* __restrict__ Wh,    // [H][4H] bf16
+    const float* __restrict__ h0, const float* __restrict__ c0,  // [B,H]
+    const unsigned char* __restrict__ done,  // [B,L]
+    float* __restrict__ h_out,           // [B,L,H]
+    float* __restrict__ h_fin, float* __restrict__ c_fin,  // [B,H]
+    float* __restrict__ acts,            // [B,L,4H]  (STASH only)
+    float* __restrict__ c_prev_st,       // [B,L,H]   (STASH only)
+    bf16raw* __restrict__ h_prev_st,   // [B,L,H]   (STASH only)
+    float forget_bias, int L, int H) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* gates = reinterpret_cast<float*>(smem);  // [4H]
+  float* hbuf = gates + 4 * H;                    // [H]
+  float* cbuf = hbuf + H;                         // [H]
+
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int G = 4 * H;
+
+  for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
+    hbuf[j] = h0[(long long)b * H + j];
+    cbuf[j] = c0[(long long)b * H + j];
+  }
+  __syncthreads();
+
+  for (int t = 0; t < L; ++t) {
+    const long long row = (long long)b * L + t;
+    // gates_h[j] = sum_k h[k] * Wh[k][j] for the column pair (2p, 2p+1);
+    // lanes on consecutive pairs
+    for (int p = tid; p < 2 * H; p += LSTM_SEQ_WIDE_BLOCK) {
+      const unsigned int* w = reinterpret_cast<const unsigned int*>(Wh) + p;
+      float ga = 0.0f, gb = 0.0f;
+#pragma unroll 8
+      for (int k = 0; k < H; ++k) {
+        const unsigned int u = w[k * 2 * H];
+        const float hk = hbuf[k];
+        ga = fmaf(hk, __uint_as_float(u << 16), ga);
+        gb = fmaf(hk, __uint_as_float(u & 0xffff0000u), gb);
+      }
+      const long long xi = row * G + 2 * p;
+      gates[2 * p] = ga + (xg16 ? lstm_b2f(xg16[xi]) : xg32[xi]);
+      gates[2 * p + 1] =
+          gb + (xg16 ? lstm_b2f(xg16[xi + 1]) : xg32[xi + 1]);
+    }
+    __syncthreads();
+    const float keep = done[row] ? 0.0f : 1.0f;
+    for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
+      const long long sb = row * H + j;
+      const float i_s = drla_sigmoid(gates[j]);
+      const float g_t = tanhf(gates[H + j]);
+      const float f_s = drla_sigmoid(gates[2 * H + j] + forget_bias);
+      const float o_s = drla_sigmoid(gates[3 * H + j]);
+      const float c_old = cbuf[j];
+      if (STASH) {
+        h_prev_st[sb] = drla_f32_to_bf16(hbuf[j]);
+        c_prev_st[sb] = c_old;
+        acts[row * G + j] = i_s;
+        acts[row * G + H + j] = g_t;
+        acts[row * G + 2 * H + j] = f_s;
+        acts[row * G + 3 * H + j] = o_s;
+      }
+      const float c_new = f_s * c_old + i_s * g_t;
+      const float h_new = o_s * tanhf(c_new);
+      h_out[sb] = h_new;
+      // done-mask reset applies to the CARRY, not the emitted h
+      hbuf[j] = h_new * keep;
+      cbuf[j] = c_new * keep;
+    }
+    __syncthreads();
+  }
+  for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
+    h_fin[(long long)b * H + j] = hbuf[j];
+    c_fin[(long long)b * H + j] = cbuf[j];
+  }
+}
+
+extern "C" __global__ __launch_bounds__(LSTM_SEQ_WIDE_BLOCK) void
+drla_lstm_seq_wide_fwd(
+    const bf16raw* __restrict__ xg16, const float* __restrict__ xg32,
+    const bf16raw* __restrict__ Wh, const float* __restrict__ h0,
+    const float* __restrict__ c0, const unsigned char* __restrict__ done,
+    float* __restrict__ h_out, float* __restrict__ h_fin,
+    float* __restrict__ c_fin, float forget_bias, int B, int L, int H) {
+  lstm_seq_wide_fwd_impl<false>(xg16, xg32, Wh, h0, c0, done, h_out, h_fin,
+                                c_fin, nullptr, nullptr, nullptr,
+                                forget_bias, L, H);
+}
+
+extern "C" __global__ __launch_bounds__(LSTM_SEQ_WIDE_BLOCK) void
+drla_lstm_seq_wide_train_fwd(
+    const bf16raw* __restrict__ xg16, const bf16raw* __restrict__ Wh,
+    const float* __restrict__ h0, const float* __restrict__ c0,
+    const unsigned char* __restrict__ done, float* __restrict__ h_out,
+    float* __restrict__ h_fin, float* __restrict__ c_fin,
+    float* __restrict__ acts, float* __restrict__ c_prev_st,
+    bf16raw* __restrict__ h_prev_st, float forget_bias, int B, int L,
+    int H) {
+  lstm_seq_wide_fwd_impl<true>(xg16, nullptr, Wh, h0, c0, done, h_out,
+                               h_fin, c_fin, acts, c_prev_st, h_prev_st,
+                               forget_bias, L, H);
+}
+
+// Backward of the wide train forward; the contract of
+// drla_lstm_seq_train_bwd. dh[j] = sum_l dg4[l] * Wh[j][l] walks ROW j of
+// Wh, so a wave owns a row: its lanes stride over l in bf16 pairs
+// (consecutive lanes on consecutive addresses), then a shuffle reduction.
+extern "C" __global__ __launch_bounds__(LSTM_SEQ_WIDE_BLOCK) void
+drla_lstm_seq_wide_train_bwd(
+    const float* __restrict__ dh_out,    // [B,L,H]
+    const float* __restrict__ dh_fin,    // [B,H] or null
+    const float* __restrict__ dc_fin,    // [B,H] or null
+    const float* __restrict__ acts,      // [B,L,4H]
+    const float* __restrict__ c_prev_st, // [B,L,H]
+    const bf16raw* __restrict__ Wh,    // [H][4H]
+    const unsigned char* __restrict__ done,  // [B,L]
+    bf16raw* __restrict__ dxg,         // [B,L,4H] gate-preact grads
+    float* __restrict__ dh0, float* __restrict__ dc0,  // [B,H]
+    int B, int L, int H) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* dg4 = reinterpret_cast<float*>(smem);  // [4H]
+  float* dhc = dg4 + 4 * H;                     // [H]
+  float* dcc = dhc + H;                         // [H]
+
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid % DRLA_WAVE;
+  const int wave = tid / DRLA_WAVE;
+  const int G = 4 * H;
+
+  for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
+    dhc[j] = dh_fin ? dh_fin[(long long)b * H + j] : 0.0f;
+    dcc[j] = dc_fin ? dc_fin[(long long)b * H + j] : 0.0f;
+  }
+  __syncthreads();
+
+  for (int t = L - 1; t >= 0; --t) {
+    const long long row = (long long)b * L + t;
+    const float keep = done[row] ? 0.0f : 1.0f;
+    for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
+      const long long ab = row * G;
+      const long long sb = row * H + j;
+      const float i_s = acts[ab + j];
+      const float g_t = acts[ab + H + j];
+      const float f_s = acts[ab + 2 * H + j];
+      const float o_s = acts[ab + 3 * H + j];
+      const float cp = c_prev_st[sb];
+      const float c_new = f_s * cp + i_s * g_t;
+      const float tc = tanhf(c_new);
+      // carry grads were stored PRE-mask; the forward applied keep_t to
+      // this step's outputs before carrying them into t+1
+      const float dh_new = dh_out[sb] + dhc[j] * keep;
+      const float d_tc = dh_new * o_s * (1.0f - tc * tc) + dcc[j] * keep;
+      const float di = d_tc * g_t;
+      const float dg = d_tc * i_s;
+      const float df = d_tc * cp;
+      const float do_ = dh_new * tc;
+      dg4[j] = di * i_s * (1.0f - i_s);
+      dg4[H + j] = dg * (1.0f - g_t * g_t);
+      dg4[2 * H + j] = df * f_s * (1.0f - f_s);
+      dg4[3 * H + j] = do_ * o_s * (1.0f - o_s);
+      dcc[j] = d_tc * f_s;  // pre-mask carry for t-1
+    }
+    __syncthreads();
+    for (int j = tid; j < G; j += LSTM_SEQ_WIDE_BLOCK) {
+      dxg[row * G + j] = drla_f32_to_bf16(dg4[j]);
+    }
+    // j is wave-uniform, so every lane of a wave reaches the shuffles
+    for (int j = wave; j < H; j += LSTM_SEQ_WIDE_BLOCK / DRLA_WAVE) {
+      const unsigned int* w =
+          reinterpret_cast<const unsigned int*>(Wh) + (long long)j * 2 * H;
+      float s = 0.0f;
+#pragma unroll 4
+      for (int q = lane; q < 2 * H; q += DRLA_WAVE) {
+        const unsigned int u = w[q];
+        s = fmaf(dg4[2 * q], __uint_as_float(u << 16), s);
+        s = fmaf(dg4[2 * q + 1], __uint_as_float(u & 0xffff0000u), s);
+      }
+      for (int off = DRLA_WAVE / 2; off > 0; off >>= 1) {
+        s += __shfl_down(s, off, DRLA_WAVE);
+      }
+      if (lane == 0) dhc[j] = s;  // pre-mask carry for t-1 (h0 unmasked)
+    }
+    __syncthreads();
+  }
+  for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
+    dh0[(long long)b * H + j] = dhc[j];
+    dc0[(long long)b * H + j] = dcc[j];
+  }
+}

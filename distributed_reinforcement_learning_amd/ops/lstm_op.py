@@ -16,6 +16,10 @@ import torch
 
 from distributed_reinforcement_learning_amd import ops as _ops
 
+# largest hidden size the LSTM sequence kernels take (ops/hip/drla_common.h
+# LSTM_SEQ_MAX_HIDDEN); the launchers refuse anything wider
+LSTM_SEQ_MAX_HIDDEN = 512
+
 
 class _FusedLstmTail(torch.autograd.Function):
     @staticmethod

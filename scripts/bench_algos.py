@@ -94,9 +94,12 @@ def bench_apex(steps=200, warmup=30):
         "batch": cfg.batch_size}), flush=True)
 
 
-def bench_r2d2(steps=200, warmup=30, n_step=1, priority_eta=None):
+def bench_r2d2(steps=200, warmup=30, n_step=1, priority_eta=None,
+               lstm_size=None):
     from distributed_reinforcement_learning_amd.agents import r2d2 as r2d2_agent
     cfg = load_config("config.json", "r2d2")
+    if lstm_size is not None:
+        cfg.lstm_size = int(lstm_size)
     dev = "cuda:0"
     agent = r2d2_agent.Agent(
         seq_len=cfg.seq_len, burn_in=cfg.burn_in,
@@ -170,7 +173,8 @@ def bench_r2d2(steps=200, warmup=30, n_step=1, priority_eta=None):
         "train_steps_per_s": 1 / dt,
         "sequences_per_s": cfg.batch_size / dt,
         "batch": cfg.batch_size, "seq_len": L, "burn_in": cfg.burn_in,
-        "n_step": n_step, "priority_eta": priority_eta}),
+        "lstm_size": cfg.lstm_size, "n_step": n_step,
+        "priority_eta": priority_eta}),
         flush=True)
 
 
