@@ -91,12 +91,29 @@ class ActionEmbedding(nn.Module):
         self.fc2 = nn.Linear(hidden, hidden)
         self.out_features = hidden
 
-    def forward(self, prev_action: torch.Tensor) -> torch.Tensor:
-        from distributed_reinforcement_learning_amd.ops import embed_op, available
+    def fused_ok(self) -> bool:
+        """True when forward() runs the fused HIP embed MLP."""
+        from distributed_reinforcement_learning_amd.ops import available
         t = self.table
-        if (t.is_cuda and t.dtype == torch.bfloat16
+        return (t.is_cuda and t.dtype == torch.bfloat16
                 and t.shape[1] == 256 and self.fc2.out_features == 256
-                and available()):
+                and available())
+
+    def forward_into(self, prev_action: torch.Tensor, xh_slab: torch.Tensor,
+                     emb_col: int, h: torch.Tensor) -> torch.Tensor:
+        """Fused path only: the embedding lands in xh_slab's columns
+        [emb_col, emb_col+256) (the returned view), bf16(h) and the pad
+        columns behind it — ops/xh_op.py."""
+        from distributed_reinforcement_learning_amd.ops import embed_op
+        assert self.fused_ok()
+        return embed_op.fused_action_embed(
+            prev_action.long(), self.table, self.bias1, self.fc2.weight,
+            self.fc2.bias, xh_slab, emb_col, h)
+
+    def forward(self, prev_action: torch.Tensor) -> torch.Tensor:
+        from distributed_reinforcement_learning_amd.ops import embed_op
+        t = self.table
+        if self.fused_ok():
             return embed_op.fused_action_embed(
                 prev_action.long(), t, self.bias1, self.fc2.weight,
                 self.fc2.bias)
@@ -245,6 +262,16 @@ class LSTMCellTF(nn.Module):
         if g.is_cuda:
             return lstm_fused_step(g, c.float(), self.forget_bias)
         return lstm_fused_step(g.float(), c.float(), self.forget_bias)
+
+    def forward_slab(self, xh: torch.Tensor, c: torch.Tensor):
+        """xh already assembled as [x | h | ones-pad] bf16 (ops/xh_op.py;
+        requires _aug_weight_ok()): the same GEMM forward_cat runs, without
+        its cat and cast."""
+        from distributed_reinforcement_learning_amd.ops.lstm_op import (
+            lstm_fused_step,
+        )
+        g = torch.mm(xh, _AugGateWeight.apply(self.weight, self.bias))
+        return lstm_fused_step(g, c.float(), self.forget_bias)
 
     def forward_xh(self, xh: torch.Tensor, c: torch.Tensor):
         from distributed_reinforcement_learning_amd.ops.lstm_op import (

@@ -52,12 +52,52 @@ class ImpalaActorCritic(nn.Module):
     def forward(self, state, prev_action, h, c):
         return self.single_step(state, prev_action, h, c)
 
+    # measurement / parity switch: False keeps the torch.cat assembly
+    USE_XH_SLAB = True
+
+    def _xh_slab_ok(self, flat_state, flat_h) -> bool:
+        """The in-place xh assembly needs all three custom producers: the
+        HIP conv stack, the fused embed MLP, and the bias-augmented gate
+        weight (its pad columns are part of the slab)."""
+        if not (self.USE_XH_SLAB and flat_state.is_cuda
+                and flat_state.dtype == torch.uint8):
+            return False
+        from distributed_reinforcement_learning_amd.ops.conv_op import (
+            custom_stack_ok,
+        )
+        return (custom_stack_ok(self.conv, flat_state)
+                and self.action_emb.fused_ok()
+                and self.lstm._aug_weight_ok()
+                and flat_h.dtype == torch.float32
+                and flat_h.shape[1] % 8 == 0)
+
     def _unroll_features(self, traj_state, traj_prev_action, traj_h, traj_c):
         B, T = traj_state.shape[:2]
         flat_state = traj_state.reshape(B * T, *traj_state.shape[2:])
         flat_pa = traj_prev_action.reshape(B * T)
         flat_h = traj_h.reshape(B * T, -1)
         flat_c = traj_c.reshape(B * T, -1)
+        if self._xh_slab_ok(flat_state, flat_h):
+            # the gate-GEMM input assembled IN PLACE: conv-l3 and the embed
+            # MLP store into one preallocated slab (the embed kernel also
+            # drops bf16(h) and the ones-pad in) — same xh as the cat below
+            # builds, minus the cat and the h cast launches (ops/xh_op.py)
+            from distributed_reinforcement_learning_amd.ops import xh_op
+            from distributed_reinforcement_learning_amd.ops.conv_op import (
+                atari_conv_stack,
+            )
+            n_conv = self.conv.out_features
+            H = flat_h.shape[1]
+            slab = torch.empty(
+                B * T, xh_op.slab_width(n_conv, self.action_emb.out_features,
+                                        H),
+                dtype=torch.bfloat16, device=flat_state.device)
+            conv_y = atari_conv_stack(self.conv, flat_state, out_slab=slab)
+            emb = self.action_emb.forward_into(flat_pa, slab, n_conv,
+                                               flat_h.contiguous())
+            xh = xh_op.assemble_xh(conv_y, emb, slab)
+            new_h, _ = self.lstm.forward_slab(xh, flat_c)
+            return new_h, B, T
         conv_out = self.conv(flat_state)
         emb = self.action_emb(flat_pa)
         # ONE cat builds the gate-GEMM input directly (conv || emb || h

@@ -60,11 +60,13 @@ STASH_INPUTS = False
 class _ConvLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, w_flat: torch.Tensor,
-                bias_f32: torch.Tensor, layer: int):
+                bias_f32: torch.Tensor, layer: int, out_slab=None):
         ext = _ops.require_ext()
         stash = STASH_INPUTS and layer <= 1
+        # out_slab: the kernel stores into the leading columns of this wider
+        # [N, R] buffer and y is that strided view (ops/xh_op.py)
         y, x_st = ext.conv_fwd(layer, x.contiguous(), w_flat.contiguous(),
-                               bias_f32.contiguous(), stash)
+                               bias_f32.contiguous(), stash, out_slab)
         ctx.save_for_backward(x_st if stash else x, w_flat, y)
         ctx.layer = layer
         return y
@@ -78,7 +80,9 @@ class _ConvLayer(torch.autograd.Function):
         # mask kernel writes bias-grad partials into a persistent slot
         # buffer; the wgrad finalize that follows sums them -> bf16 dbias
         if not (dy.is_contiguous() or (dy.stride(-1) == 1
-                                        and dy.dim() >= 2)):
+                                        and dy.dim() >= 2
+                                        and dy.stride(0) % 8 == 0
+                                        and dy.storage_offset() % 8 == 0)):
             dy = dy.contiguous()
         dy_m = ext.relu_mask_bwd(dy, y, co, layer)
         if _side_enabled():
@@ -99,11 +103,11 @@ class _ConvLayer(torch.autograd.Function):
         dx = None
         if layer >= 2 and ctx.needs_input_grad[0]:
             dx = ext.conv_dgrad(layer, dy_m, w_flat)
-        return dx, dw, dbias, None
+        return dx, dw, dbias, None, None
 
 
 def conv_layer(x: torch.Tensor, conv: torch.nn.Conv2d,
-               layer: int) -> torch.Tensor:
+               layer: int, out_slab=None) -> torch.Tensor:
     """x NHWC (u8 for layers 0/1, bf16 for 2/3); returns NHWC bf16 output.
 
     conv.weight must be bf16 channels_last ([CO][KH][KW][CI] physically) —
@@ -112,18 +116,23 @@ def conv_layer(x: torch.Tensor, conv: torch.nn.Conv2d,
     w = conv.weight
     co = w.shape[0]
     w_flat = w.permute(0, 2, 3, 1).reshape(co, -1)
-    return _ConvLayer.apply(x, w_flat, conv.bias, layer)
+    return _ConvLayer.apply(x, w_flat, conv.bias, layer, out_slab)
 
 
-def atari_conv_stack(stack, x_u8_nhwc: torch.Tensor) -> torch.Tensor:
+def atari_conv_stack(stack, x_u8_nhwc: torch.Tensor,
+                     out_slab=None) -> torch.Tensor:
     """Full custom stack: u8 [N,84,84,C] -> flat [N,3136] bf16 features,
     flattened in NHWC order (identical to the torch path in
-    models/blocks.AtariConvStack)."""
+    models/blocks.AtariConvStack). With out_slab ([N, R >= 3136] bf16) the
+    last layer stores straight into the slab's leading columns and the
+    NHWC [N,7,7,64] strided view of them is returned unflattened."""
     ci = x_u8_nhwc.shape[-1]
     l1 = 0 if ci == 4 else 1
     y = conv_layer(x_u8_nhwc, stack.conv1, l1)
     y = conv_layer(y, stack.conv2, 2)
-    y = conv_layer(y, stack.conv3, 3)
+    y = conv_layer(y, stack.conv3, 3, out_slab)
+    if out_slab is not None:
+        return y
     return y.reshape(y.shape[0], -1)
 
 

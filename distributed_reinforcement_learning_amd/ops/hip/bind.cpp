@@ -151,14 +151,35 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
 
 std::tuple<torch::Tensor, torch::Tensor> conv_fwd(
     int layer, torch::Tensor in, torch::Tensor w, torch::Tensor bias,
-    bool stash_input) {
+    bool stash_input, c10::optional<torch::Tensor> out_slab) {
   check_gpu_contig(in, "in");
   check_gpu_contig(w, "w");
   check_gpu_contig(bias, "bias");
   const auto& cfg = conv_layer(layer);
   const int batch = in.size(0);
-  auto out = torch::empty({batch, cfg.ho, cfg.wo, cfg.co},
-                          in.options().dtype(torch::kBFloat16));
+  // out_slab (bf16 layers): a wider row-major [batch, R] bf16 buffer whose
+  // leading ho*wo*co columns receive the output; the returned y is that
+  // strided view (the gate-GEMM input is assembled in place, no cat)
+  torch::Tensor out;
+  long long out_n_stride = 0;
+  if (out_slab.has_value()) {
+    const auto& slab = *out_slab;
+    const long long row = (long long)cfg.ho * cfg.wo * cfg.co;
+    TORCH_CHECK(layer >= 2, "out_slab is a bf16-layer feature");
+    TORCH_CHECK(slab.is_cuda() && slab.dim() == 2 &&
+                    slab.scalar_type() == torch::kBFloat16 &&
+                    slab.size(0) == batch && slab.size(1) >= row &&
+                    slab.stride(1) == 1 && slab.stride(0) >= slab.size(1),
+                "out_slab must be a row-major [batch, >= ho*wo*co] bf16 "
+                "buffer");
+    out_n_stride = slab.stride(0);
+    out = slab.as_strided(
+        {batch, cfg.ho, cfg.wo, cfg.co},
+        {out_n_stride, (long long)cfg.wo * cfg.co, cfg.co, 1});
+  } else {
+    out = torch::empty({batch, cfg.ho, cfg.wo, cfg.co},
+                       in.options().dtype(torch::kBFloat16));
+  }
   const dim3 grid(conv_m_tiles(batch * cfg.ho * cfg.wo));
   // stashed-input mode (u8 layers only): the kernel bundles a
   // pass-through copy of the input so the backward never re-reads the
@@ -178,7 +199,7 @@ std::tuple<torch::Tensor, torch::Tensor> conv_fwd(
   } else {
     hipLaunchKernelGGL(kConvFwdBf16[layer - 2], grid, dim3(DRLA_CONV_BLOCK),
                        0, cur_stream(), BF16P(in), BF16P(w), BF16P(bias),
-                       BF16PM(out), batch);
+                       BF16PM(out), batch, out_n_stride);
   }
   return {out, x_stash};
 }
@@ -203,28 +224,30 @@ static torch::Tensor& dbias_slot_buf(const torch::Tensor& like,
 
 torch::Tensor relu_mask_bwd(torch::Tensor dy, torch::Tensor y, int64_t CO,
                             int64_t slot_id) {
-  check_gpu_contig(y, "y");
-  TORCH_CHECK(dy.is_cuda(), "dy must be on GPU");
-  // dy may be an N-strided view (slice of the fused xh grad): inner dims
-  // contiguous, only stride(0) loose
-  long long n_stride, row_elems;
-  if (dy.is_contiguous()) {
-    n_stride = row_elems = dy.numel() / dy.size(0);
-  } else {
-    row_elems = 1;
-    for (int d = 1; d < dy.dim(); ++d) {
-      TORCH_CHECK(dy.stride(d - 1) >= dy.stride(d), "dy must be row-major");
-      row_elems *= dy.size(d);
+  TORCH_CHECK(dy.is_cuda() && y.is_cuda(), "dy and y must be on GPU");
+  TORCH_CHECK(dy.numel() == y.numel() && dy.size(0) == y.size(0),
+              "dy and y must hold the same rows");
+  // dy may be an N-strided view (slice of the fused xh grad) and y one too
+  // (a conv output living in the xh slab): inner dims contiguous, only
+  // stride(0) loose. Returns stride(0) in elements.
+  long long row_elems = dy.numel() / std::max<int64_t>(dy.size(0), 1);
+  auto n_stride_of = [row_elems](const torch::Tensor& t, const char* name) {
+    if (t.is_contiguous()) return row_elems;
+    for (int d = 1; d < t.dim(); ++d) {
+      TORCH_CHECK(t.stride(d - 1) >= t.stride(d), name, " must be row-major");
     }
-    TORCH_CHECK(dy.stride(dy.dim() - 1) == 1 &&
-                    dy.stride(0) >= row_elems && row_elems % 8 == 0,
-                "dy view must be inner-contiguous");
-    for (int d = 1; d + 1 < dy.dim(); ++d) {
-      TORCH_CHECK(dy.stride(d) == dy.size(d + 1) * dy.stride(d + 1),
-                  "dy inner dims must be contiguous");
+    TORCH_CHECK(t.stride(t.dim() - 1) == 1 && t.stride(0) >= row_elems &&
+                    row_elems % 8 == 0 && t.stride(0) % 8 == 0 &&
+                    t.storage_offset() % 8 == 0,
+                name, " view must be inner-contiguous and 16 B aligned");
+    for (int d = 1; d + 1 < t.dim(); ++d) {
+      TORCH_CHECK(t.stride(d) == t.size(d + 1) * t.stride(d + 1), name,
+                  " inner dims must be contiguous");
     }
-    n_stride = dy.stride(0);
-  }
+    return (long long)t.stride(0);
+  };
+  const long long n_stride = n_stride_of(dy, "dy");
+  const long long y_n_stride = n_stride_of(y, "y");
   auto out = torch::empty(dy.sizes(), dy.options());
   auto& slots = dbias_slot_buf(dy, slot_id);
   const long long n = dy.numel();
@@ -234,7 +257,7 @@ torch::Tensor relu_mask_bwd(torch::Tensor dy, torch::Tensor y, int64_t CO,
   hipLaunchKernelGGL(drla_relu_mask_bwd, dim3(grid), dim3(DRLA_BLOCK),
                      0, cur_stream(), BF16P(dy), BF16P(y), BF16PM(out),
                      slots.data_ptr<float>(), n, (int)CO, n_stride,
-                     row_elems);
+                     row_elems, y_n_stride);
   return out;
 }
 
@@ -647,7 +670,8 @@ torch::Tensor embed_bwd(torch::Tensor indices, torch::Tensor grad_out,
 std::vector<torch::Tensor> vtrace_loss_fwd(
     torch::Tensor logits, torch::Tensor value, torch::Tensor mu,
     torch::Tensor actions, torch::Tensor rewards, torch::Tensor done,
-    double gamma, int64_t clip_mode, double c_bl, double c_ent) {
+    double gamma, int64_t clip_mode, double c_bl, double c_ent,
+    bool nofill, bool stash_actions) {
   check_all_gpu_contig("vtrace_loss input", logits, value, mu, actions,
                        rewards, done);
   TORCH_CHECK(actions.scalar_type() == torch::kInt, "actions must be int32");
@@ -660,7 +684,38 @@ std::vector<torch::Tensor> vtrace_loss_fwd(
   auto p_stash = torch::empty({B, T, A}, fopt);
   auto vs_stash = torch::empty({B, T - 2}, fopt);
   auto adv_stash = torch::empty({B, T - 2}, fopt);
-  auto losses = torch::zeros({4}, fopt);  // blocks atomicAdd into it
+  // nofill: per-block partials + a ticket counter in persistent buffers
+  // (zeroed once here; the kernel's last block restores the counter), so
+  // losses needs no zero-fill launch. Default: blocks atomicAdd into a
+  // zeroed losses.
+  torch::Tensor losses, act_stash;
+  float* partials_ptr = nullptr;
+  unsigned int* counter_ptr = nullptr;
+  if (nofill) {
+    static torch::Tensor partials, counter;
+    // a captured graph keeps the addresses it was captured with, so a
+    // replaced pair is retired, never freed (64 KB covers B <= 4096)
+    static std::vector<torch::Tensor> retired;
+    if (!partials.defined() || partials.size(0) < B ||
+        partials.device() != value.device()) {
+      if (partials.defined()) {
+        retired.push_back(partials);
+        retired.push_back(counter);
+      }
+      partials = torch::zeros({std::max<int64_t>(B, 4096), 4}, fopt);
+      counter = torch::zeros({1}, fopt.dtype(torch::kInt));
+    }
+    partials_ptr = partials.data_ptr<float>();
+    counter_ptr = reinterpret_cast<unsigned int*>(counter.data_ptr<int>());
+    losses = torch::empty({4}, fopt);
+  } else {
+    losses = torch::zeros({4}, fopt);
+  }
+  int* act_stash_ptr = nullptr;
+  if (stash_actions) {
+    act_stash = torch::empty_like(actions);
+    act_stash_ptr = act_stash.data_ptr<int>();
+  }
   hipLaunchKernelGGL(
       drla_vtrace_loss_fwd, dim3(B), dim3(256), 0, cur_stream(),
       lg.bf16, lg.f32, value.data_ptr<float>(), mu.data_ptr<float>(),
@@ -668,7 +723,9 @@ std::vector<torch::Tensor> vtrace_loss_fwd(
       static_cast<float>(gamma), (int)clip_mode, static_cast<float>(c_bl),
       static_cast<float>(c_ent), p_stash.data_ptr<float>(),
       vs_stash.data_ptr<float>(), adv_stash.data_ptr<float>(),
-      losses.data_ptr<float>(), B, T, A);
+      losses.data_ptr<float>(), B, T, A, partials_ptr, counter_ptr,
+      act_stash_ptr);
+  if (stash_actions) return {losses, p_stash, vs_stash, adv_stash, act_stash};
   return {losses, p_stash, vs_stash, adv_stash};
 }
 
@@ -695,8 +752,11 @@ std::tuple<torch::Tensor, torch::Tensor> vtrace_loss_bwd(
   return {dlogits, dvalue};
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_tail_fwd(
-    torch::Tensor gates, torch::Tensor c_prev, double forget_bias) {
+// stash_c: also returns a copy of c_prev made in-kernel (4th element) for a
+// backward that must not re-read the caller's c_prev buffer
+std::vector<torch::Tensor> lstm_tail_fwd(
+    torch::Tensor gates, torch::Tensor c_prev, double forget_bias,
+    bool stash_c) {
   check_gpu_contig(gates, "gates");
   check_gpu_contig(c_prev, "c_prev");
   const bool bf16 = gates.scalar_type() == torch::kBFloat16;
@@ -712,20 +772,27 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_tail_fwd(
   auto new_c = torch::empty_like(c_prev);
   auto stash = torch::empty({N, (long long)H4},
                             c_prev.options().dtype(torch::kFloat));
+  torch::Tensor c_stash;
+  float* c_stash_ptr = nullptr;
+  if (stash_c) {
+    c_stash = torch::empty_like(c_prev);
+    c_stash_ptr = c_stash.data_ptr<float>();
+  }
   if (bf16) {
     hipLaunchKernelGGL(drla_lstm_tail_fwd_bf16, dim3(drla_grid(N * H)),
                        dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(gates),
                        c_prev.data_ptr<float>(), new_h.data_ptr<float>(),
                        new_c.data_ptr<float>(), stash.data_ptr<float>(),
-                       static_cast<float>(forget_bias), N, H);
+                       static_cast<float>(forget_bias), N, H, c_stash_ptr);
   } else {
     hipLaunchKernelGGL(drla_lstm_tail_fwd, dim3(drla_grid(N * H)),
                        dim3(DRLA_BLOCK), 0, cur_stream(),
                        gates.data_ptr<float>(), c_prev.data_ptr<float>(),
                        new_h.data_ptr<float>(), new_c.data_ptr<float>(),
                        stash.data_ptr<float>(),
-                       static_cast<float>(forget_bias), N, H);
+                       static_cast<float>(forget_bias), N, H, c_stash_ptr);
   }
+  if (stash_c) return {new_h, new_c, stash, c_stash};
   return {new_h, new_c, stash};
 }
 
@@ -774,7 +841,11 @@ int mh_row_tiles(int N) { return (N + MH_BM - 1) / MH_BM; }
 
 std::vector<torch::Tensor> mlp_heads_fwd(
     torch::Tensor h, std::vector<torch::Tensor> weights,
-    std::vector<torch::Tensor> biases, int64_t A) {
+    std::vector<torch::Tensor> biases, int64_t A, bool want_bwd_bufs) {
+  // want_bwd_bufs: the kernel also zeroes the backward's f32 workspace and
+  // writes the packed W^T (the mlp_heads_pack_wt layout); both are appended
+  // to the result, and the backward then needs neither a fill nor a pack
+  // launch (mlp_heads_bwd's ws argument)
   check_gpu_contig(h, "h");
   TORCH_CHECK(weights.size() == 6 && biases.size() == 6);
   for (auto& t : weights) check_gpu_contig(t, "W");
@@ -785,6 +856,16 @@ std::vector<torch::Tensor> mlp_heads_fwd(
   auto logits = torch::empty({N, A}, bopt);
   auto value = torch::empty({N}, h.options().dtype(torch::kFloat));
   auto stash = torch::empty({N, 5 * 256}, bopt);
+  torch::Tensor ws, wt;
+  float* ws_ptr = nullptr;
+  bf16raw* wt_ptr = nullptr;
+  if (want_bwd_bufs) {
+    ws = torch::empty({(long long)N * 256 + 4 * 256 + A + 1},
+                      h.options().dtype(torch::kFloat));
+    wt = torch::empty({4 * 65536 + 256 * 32 + 256}, bopt);
+    ws_ptr = ws.data_ptr<float>();
+    wt_ptr = BF16PM(wt);
+  }
   hipLaunchKernelGGL(
       drla_mlp_heads_fwd, dim3(mh_row_tiles(N), 2), dim3(256), 0,
       cur_stream(), h.data_ptr<float>(),
@@ -792,13 +873,18 @@ std::vector<torch::Tensor> mlp_heads_fwd(
       BF16P(biases[1]), BF16P(weights[2]), BF16P(biases[2]),
       BF16P(weights[3]), BF16P(biases[3]), BF16P(weights[4]),
       BF16P(biases[4]), BF16P(weights[5]), BF16P(biases[5]),
-      BF16PM(logits), value.data_ptr<float>(), BF16PM(stash), N, (int)A);
+      BF16PM(logits), value.data_ptr<float>(), BF16PM(stash), N, (int)A,
+      wt_ptr, ws_ptr);
+  if (want_bwd_bufs) return {logits, value, stash, ws, wt};
   return {logits, value, stash};
 }
 
+// ws_opt: the workspace a want_bwd_bufs forward already zeroed (one use per
+// forward: the kernel accumulates into it); absent -> zero-filled here
 std::vector<torch::Tensor> mlp_heads_bwd(
     torch::Tensor dlogits, torch::Tensor dvalue, torch::Tensor stash,
-    std::vector<torch::Tensor> weights, int64_t A) {
+    std::vector<torch::Tensor> weights, int64_t A,
+    c10::optional<torch::Tensor> ws_opt) {
   check_gpu_contig(dlogits, "dlogits");
   check_gpu_contig(dvalue, "dvalue");
   check_gpu_contig(stash, "stash");
@@ -813,7 +899,15 @@ std::vector<torch::Tensor> mlp_heads_bwd(
   // dh + all six bias grads live in ONE zeroed workspace (atomics targets;
   // one fill kernel instead of seven)
   const long long ws_n = (long long)N * 256 + 4 * 256 + A + 1;
-  auto ws = torch::zeros({ws_n}, fopt);
+  torch::Tensor ws;
+  if (ws_opt.has_value()) {
+    ws = *ws_opt;
+    check_gpu_contig(ws, "ws");
+    TORCH_CHECK(ws.scalar_type() == torch::kFloat && ws.numel() == ws_n,
+                "ws must be f32 [N*256 + 4*256 + A + 1]");
+  } else {
+    ws = torch::zeros({ws_n}, fopt);
+  }
   long long off = 0;
   auto dh = ws.narrow(0, off, (long long)N * 256).view({N, 256});
   off += (long long)N * 256;
@@ -838,54 +932,128 @@ std::vector<torch::Tensor> mlp_heads_bwd(
           db3v, ws};
 }
 
-std::tuple<torch::Tensor, torch::Tensor> embed_mlp_fwd(
+// Returns {out, a1}, then the in-kernel copy of the clamped indices when
+// stash_idx, then W2^T ([256,256], for embed_mlp_bwd's w2t argument) when
+// want_w2t.
+std::vector<torch::Tensor> embed_mlp_fwd(
     torch::Tensor pa, torch::Tensor table, torch::Tensor b1,
-    torch::Tensor w2, torch::Tensor b2) {
+    torch::Tensor w2, torch::Tensor b2, bool stash_idx, bool want_w2t,
+    c10::optional<torch::Tensor> xh_slab, int64_t emb_col,
+    c10::optional<torch::Tensor> h_opt) {
   check_all_gpu_contig("embed fwd input", pa, table, b1, w2, b2);
   TORCH_CHECK(pa.scalar_type() == torch::kLong, "pa must be int64");
   const int N = pa.numel();
   auto bopt = table.options();
-  auto out = torch::empty({N, 256}, bopt);
+  // xh_slab: the gate-GEMM input [N, emb_col + 256 + H + 8] bf16, assembled
+  // in place — out becomes the slab's columns [emb_col, emb_col + 256) and
+  // the kernel also writes bf16(h) and the (1, 0 x 7) pad after them
+  torch::Tensor out;
+  long long slab_stride = 0;
+  const float* h_ptr = nullptr;
+  int H = 0;
+  if (xh_slab.has_value()) {
+    const auto& slab = *xh_slab;
+    TORCH_CHECK(h_opt.has_value(), "xh_slab needs h");
+    const auto& h = *h_opt;
+    check_gpu_contig(h, "h");
+    check_gpu_contig(slab, "xh_slab");
+    TORCH_CHECK(h.scalar_type() == torch::kFloat && h.dim() == 2 &&
+                    h.size(0) == N && h.size(1) % 8 == 0,
+                "h must be f32 [N, H], H % 8 == 0");
+    H = h.size(1);
+    TORCH_CHECK(slab.dim() == 2 && slab.scalar_type() == torch::kBFloat16 &&
+                    slab.size(0) == N && emb_col >= 0 && emb_col % 8 == 0 &&
+                    slab.size(1) == emb_col + 256 + H + 8 &&
+                    slab.storage_offset() % 8 == 0,
+                "xh_slab must be bf16 [N, emb_col + 256 + H + 8]");
+    slab_stride = slab.stride(0);
+    h_ptr = h.data_ptr<float>();
+    out = slab.narrow(1, emb_col, 256);
+  } else {
+    out = torch::empty({N, 256}, bopt);
+  }
   auto a1 = torch::empty({N, 256}, bopt);
+  std::vector<torch::Tensor> res = {out, a1};
+  long long* idx_ptr = nullptr;
+  bf16raw* w2t_ptr = nullptr;
+  if (stash_idx) {
+    res.push_back(torch::empty({N}, pa.options()));
+    idx_ptr = reinterpret_cast<long long*>(res.back().data_ptr<int64_t>());
+  }
+  if (want_w2t) {
+    res.push_back(torch::empty({256, 256}, bopt));
+    w2t_ptr = BF16PM(res.back());
+  }
   hipLaunchKernelGGL(drla_embed_mlp_fwd, dim3(mh_row_tiles(N)), dim3(256), 0,
                      cur_stream(), i64p(pa), BF16P(table), BF16P(b1),
                      BF16P(w2), BF16P(b2), BF16PM(out), BF16PM(a1), N,
-                     (int)table.size(0));
-  return {out, a1};
+                     (int)table.size(0), idx_ptr, w2t_ptr, slab_stride, h_ptr,
+                     H);
+  return res;
 }
 
+// w2t_opt: W2^T from a want_w2t forward (skips the pack launch).
+// fuse_scatter: the table scatter runs in the dgrad kernel's epilogue (no
+// da1 round trip, no scatter launch).
 std::vector<torch::Tensor> embed_mlp_bwd(torch::Tensor dy, torch::Tensor out,
                                          torch::Tensor a1, torch::Tensor w2,
-                                         torch::Tensor idx, int64_t A) {
-  check_all_gpu_contig("embed bwd input", out, a1, w2);
+                                         torch::Tensor idx, int64_t A,
+                                         c10::optional<torch::Tensor> w2t_opt,
+                                         bool fuse_scatter) {
+  check_all_gpu_contig("embed bwd input", a1, w2);
   check_gpu_contig(idx, "idx");
+  // out (the ReLU-2 mask) may be a column slice of the xh slab
+  TORCH_CHECK(out.is_cuda() && out.dim() == 2 && out.size(1) == 256 &&
+                  out.stride(1) == 1 && out.stride(0) >= 256,
+              "out must be row-contiguous [N,256]");
+  const long long out_stride = out.stride(0);
+  TORCH_CHECK(idx.scalar_type() == torch::kLong && idx.numel() == out.size(0),
+              "idx must be int64 [N]");
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 2 && dy.stride(1) == 1,
               "dy must be row-contiguous");
   const int N = out.size(0);
   const long long n_table = (long long)A * 256;
-  auto bopt = out.options();
+  auto bopt = a1.options();
   // persistent buffers: W2^T (fully overwritten) and the f32 partial
   // scratch (zero-between-calls; drla_embed_finalize re-zeroes it)
-  static torch::Tensor w2t, scratch;
-  if (!w2t.defined()) w2t = torch::empty({65536}, bopt);
+  static torch::Tensor w2t_own, scratch;
   if (!scratch.defined() || scratch.numel() != n_table + 512) {
     scratch = torch::zeros({n_table + 512}, bopt.dtype(torch::kFloat));
   }
-  hipLaunchKernelGGL(drla_embed_w2t_pack, dim3(drla_grid(65536)),
-                     dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(w2),
-                     BF16PM(w2t));
+  torch::Tensor w2t;
+  if (w2t_opt.has_value()) {
+    w2t = *w2t_opt;
+    check_gpu_contig(w2t, "w2t");
+    TORCH_CHECK(w2t.numel() == 65536 && w2t.scalar_type() == w2.scalar_type(),
+                "w2t must be bf16 [256,256]");
+  } else {
+    if (!w2t_own.defined()) w2t_own = torch::empty({65536}, bopt);
+    w2t = w2t_own;
+    hipLaunchKernelGGL(drla_embed_w2t_pack, dim3(drla_grid(65536)),
+                       dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(w2),
+                       BF16PM(w2t));
+  }
   auto dz2 = torch::empty({N, 256}, bopt);
-  auto da1 = torch::empty({N, 256}, bopt);
   float* bias_ws = scratch.data_ptr<float>() + n_table;
-  hipLaunchKernelGGL(drla_embed_mlp_bwd, dim3(mh_row_tiles(N)), dim3(256), 0,
-                     cur_stream(), BF16P(dy), (long long)dy.stride(0),
-                     BF16P(out), BF16P(a1), BF16P(w2t), BF16PM(dz2),
-                     BF16PM(da1), bias_ws, N);
-  // table scatter into the f32 scratch, then one 3-output finalize
-  hipLaunchKernelGGL(
-      drla_embed_bwd_scatter, dim3(drla_grid((long long)N * 256)),
-      dim3(DRLA_BLOCK), 0, cur_stream(), i64p(idx), BF16P(da1), nullptr,
-      scratch.data_ptr<float>(), N, 256, (long long)A);
+  if (fuse_scatter) {
+    hipLaunchKernelGGL(drla_embed_mlp_bwd, dim3(mh_row_tiles(N)), dim3(256),
+                       0, cur_stream(), BF16P(dy), (long long)dy.stride(0),
+                       BF16P(out), BF16P(a1), BF16P(w2t), BF16PM(dz2),
+                       (bf16raw*)nullptr, bias_ws, N, i64p(idx),
+                       scratch.data_ptr<float>(), (int)A, out_stride);
+  } else {
+    auto da1 = torch::empty({N, 256}, bopt);
+    hipLaunchKernelGGL(drla_embed_mlp_bwd, dim3(mh_row_tiles(N)), dim3(256),
+                       0, cur_stream(), BF16P(dy), (long long)dy.stride(0),
+                       BF16P(out), BF16P(a1), BF16P(w2t), BF16PM(dz2),
+                       BF16PM(da1), bias_ws, N, (const long long*)nullptr,
+                       (float*)nullptr, (int)A, out_stride);
+    // table scatter into the f32 scratch, then one 3-output finalize
+    hipLaunchKernelGGL(
+        drla_embed_bwd_scatter, dim3(drla_grid((long long)N * 256)),
+        dim3(DRLA_BLOCK), 0, cur_stream(), i64p(idx), BF16P(da1), nullptr,
+        scratch.data_ptr<float>(), N, 256, (long long)A);
+  }
   auto dtable = torch::empty({A, 256}, bopt);
   auto db1 = torch::empty({256}, bopt);
   auto db2 = torch::empty({256}, bopt);
@@ -1207,12 +1375,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "uint8 frames -> bf16/255 (K11)");
   m.def("vtrace_scan", &vtrace_scan, "fused V-trace reverse scan (K5)");
   m.def("vtrace_loss_fwd", &vtrace_loss_fwd,
-        "fused IMPALA loss pipeline forward (K5+K7+K13)");
+        "fused IMPALA loss pipeline forward (K5+K7+K13); nofill: ticketed "
+        "fixed-order loss sums, no zero-fill; stash_actions: also returns "
+        "a copy of actions made in-kernel",
+        py::arg("logits"), py::arg("value"), py::arg("mu"),
+        py::arg("actions"), py::arg("rewards"), py::arg("done"),
+        py::arg("gamma"), py::arg("clip_mode"), py::arg("c_bl"),
+        py::arg("c_ent"), py::arg("nofill") = false,
+        py::arg("stash_actions") = false);
   m.def("vtrace_loss_bwd", &vtrace_loss_bwd,
         "fused IMPALA loss pipeline backward (closed form)");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("conv_fwd", &conv_fwd,
-        "MFMA implicit-GEMM conv fwd, fused normalize+bias+ReLU (K1)");
+        "MFMA implicit-GEMM conv fwd, fused normalize+bias+ReLU (K1)",
+        py::arg("layer"), py::arg("x"), py::arg("w"), py::arg("bias"),
+        py::arg("stash_input"), py::arg("out_slab") = py::none());
   m.def("conv_wgrad", &conv_wgrad, "MFMA conv weight gradient (K1 bwd)");
   m.def("conv_dgrad", &conv_dgrad, "MFMA conv data gradient (K1 bwd)");
   m.def("relu_mask_bwd", &relu_mask_bwd,
@@ -1245,16 +1422,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "GPU PER interior-sum rebuild (float32 drift repair)");
   m.def("embed_bwd", &embed_bwd,
         "action-embedding table gradient (K2 backward)");
-  m.def("lstm_tail_fwd", &lstm_tail_fwd, "fused LSTM gate tail fwd (K3)");
+  m.def("lstm_tail_fwd", &lstm_tail_fwd, "fused LSTM gate tail fwd (K3)",
+        py::arg("gates"), py::arg("c_prev"), py::arg("forget_bias"),
+        py::arg("stash_c") = false);
   m.def("lstm_tail_bwd", &lstm_tail_bwd, "fused LSTM gate tail bwd (K3)");
   m.def("mlp_heads_fwd", &mlp_heads_fwd,
-        "fused policy+value MLP heads forward (K4)");
+        "fused policy+value MLP heads forward (K4)",
+        py::arg("h"), py::arg("weights"), py::arg("biases"), py::arg("A"),
+        py::arg("want_bwd_bufs") = false);
   m.def("mlp_heads_bwd", &mlp_heads_bwd,
-        "fused heads dgrad chain + ReLU masks + bias grads (K4 bwd)");
+        "fused heads dgrad chain + ReLU masks + bias grads (K4 bwd)",
+        py::arg("dlogits"), py::arg("dvalue"), py::arg("stash"),
+        py::arg("weights"), py::arg("A"), py::arg("ws") = py::none());
   m.def("embed_mlp_fwd", &embed_mlp_fwd,
-        "fused action-embedding MLP forward (K2)");
+        "fused action-embedding MLP forward (K2)",
+        py::arg("pa"), py::arg("table"), py::arg("b1"), py::arg("w2"),
+        py::arg("b2"), py::arg("stash_idx") = false,
+        py::arg("want_w2t") = false, py::arg("xh_slab") = py::none(),
+        py::arg("emb_col") = 0, py::arg("h") = py::none());
   m.def("embed_mlp_bwd", &embed_mlp_bwd,
-        "fused action-embedding MLP backward (K2 bwd)");
+        "fused action-embedding MLP backward (K2 bwd)",
+        py::arg("dy"), py::arg("out"), py::arg("a1"), py::arg("w2"),
+        py::arg("idx"), py::arg("A"), py::arg("w2t") = py::none(),
+        py::arg("fuse_scatter") = false);
   m.def("mlp_heads_pack_wt", &mlp_heads_pack_wt,
         "one-kernel transposed-weight pack for the heads dgrad");
   m.def("mlp_heads_wgrad", &mlp_heads_wgrad,

@@ -65,7 +65,11 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
                               const bf16raw* __restrict__ bias,  // [CO]
                               bf16raw* __restrict__ out,       // [M][CO]
                               int batch,
-                              IN_T* __restrict__ x_stash = nullptr) {
+                              IN_T* __restrict__ x_stash = nullptr,
+                              long long out_n_stride = 0) {
+  // out_n_stride != 0: sample n's HO*WO*CO outputs start at
+  // out + n*out_n_stride (the leading columns of a wider row-major slab)
+  // instead of being packed back to back
   constexpr int K = KH * KW * CI;
   constexpr int BM = DRLA_CONV_BM;
   constexpr int BK = 32;
@@ -228,15 +232,19 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
   }
 
   // ---- epilogue: bias + ReLU, bf16 NHWC store ----
+  // one addressing path: packed output is the row stride HO*WO*CO
+  if (out_n_stride == 0) out_n_stride = (long long)HO * WO * CO;
   for (int mi = 0; mi < 2; ++mi) {
-    for (int ni = 0; ni < NFRAG; ++ni) {
-      const int col = ni * 16 + (lane & 15);
-      const float b = BiasBuf[col];
-      for (int r = 0; r < 4; ++r) {
-        const int grow = row0 + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
-        if (grow < M) {
-          const float v = fmaxf(acc[mi][ni][r] + b, 0.0f);
-          out[(long long)grow * CO + col] = drla_f32_to_bf16(v);
+    for (int r = 0; r < 4; ++r) {
+      const int grow = row0 + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
+      if (grow < M) {
+        const int n = grow / (HO * WO);
+        bf16raw* orow = out + (long long)n * out_n_stride +
+                        (grow - n * (HO * WO)) * CO + (lane & 15);
+        for (int ni = 0; ni < NFRAG; ++ni) {
+          const float v =
+              fmaxf(acc[mi][ni][r] + BiasBuf[ni * 16 + (lane & 15)], 0.0f);
+          orow[ni * 16] = drla_f32_to_bf16(v);
         }
       }
     }
@@ -282,14 +290,16 @@ CONV_KERNEL drla_conv_fwd_l1_c1(
 
 CONV_KERNEL drla_conv_fwd_l2(
     const bf16raw* in, const bf16raw* w, const bf16raw* bias, bf16raw* out,
-    int batch) {
-  conv_fwd_impl<bf16raw, DRLA_CONV_GEOM(2)>(in, w, bias, out, batch);
+    int batch, long long out_n_stride) {
+  conv_fwd_impl<bf16raw, DRLA_CONV_GEOM(2)>(in, w, bias, out, batch, nullptr,
+                                            out_n_stride);
 }
 
 CONV_KERNEL drla_conv_fwd_l3(
     const bf16raw* in, const bf16raw* w, const bf16raw* bias, bf16raw* out,
-    int batch) {
-  conv_fwd_impl<bf16raw, DRLA_CONV_GEOM(3)>(in, w, bias, out, batch);
+    int batch, long long out_n_stride) {
+  conv_fwd_impl<bf16raw, DRLA_CONV_GEOM(3)>(in, w, bias, out, batch, nullptr,
+                                            out_n_stride);
 }
 
 // ---------------------------------------------------------------------------
@@ -312,7 +322,9 @@ CONV_KERNEL drla_conv_fwd_l3(
 extern "C" __global__ void drla_relu_mask_bwd(
     const bf16raw* __restrict__ dy, const bf16raw* __restrict__ y,
     bf16raw* __restrict__ out, float* __restrict__ dbias_slots,
-    long long n, int CO, long long n_stride, long long row_elems) {
+    long long n, int CO, long long n_stride, long long row_elems,
+    long long y_n_stride) {  // same treatment for y (a conv output that
+                             // lives in the leading columns of the xh slab)
   // vectorized: each thread moves 8 bf16 per iteration (uint4), which pins
   // it to ONE 8-column group because stride*8 % CO == 0 (CO in {32,64},
   // blockDim 256). Per-thread acc[8] -> LDS -> one atomicAdd per (block,
@@ -341,14 +353,17 @@ extern "C" __global__ void drla_relu_mask_bwd(
   }
   const long long row8 = row_elems / 8;
   const bool strided = (n_stride != row_elems);
+  const bool y_strided = (y_n_stride != row_elems);
   for (; i < n8; i += stride) {
-    long long si = i;
-    if (strided) {
+    long long si = i, yi = i;
+    if (strided || y_strided) {
       const long long r = i / row8;
-      si = (r * n_stride + (i - r * row8) * 8) / 8;
+      const long long c8 = i - r * row8;
+      if (strided) si = (r * n_stride) / 8 + c8;
+      if (y_strided) yi = (r * y_n_stride) / 8 + c8;
     }
     const uint4 dv = dy4[si];
-    const uint4 yv = y4[i];
+    const uint4 yv = y4[yi];
     uint4 ov;
     DRLA_RM_LANE(dv.x, yv.x, ov.x, acc[0], acc[1]);
     DRLA_RM_LANE(dv.y, yv.y, ov.y, acc[2], acc[3]);

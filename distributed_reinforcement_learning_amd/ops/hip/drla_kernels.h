@@ -33,7 +33,7 @@ DRLA_KERNEL drla_vtrace_scan(const float*, const float*, const float*,
 DRLA_KERNEL drla_vtrace_loss_fwd(
     const bf16raw*, const float*, const float*, const float*, const int*,
     const float*, const unsigned char*, float, int, float, float, float*,
-    float*, float*, float*, int, int, int);
+    float*, float*, float*, int, int, int, float*, unsigned int*, int*);
 DRLA_KERNEL drla_vtrace_loss_bwd(
     const float*, const float*, const float*, const float*, const int*,
     const float*, int, float, float, bf16raw*, float*, float*, int, int,
@@ -41,12 +41,13 @@ DRLA_KERNEL drla_vtrace_loss_bwd(
 
 // ---- lstm_gates.hip -------------------------------------------------------
 DRLA_KERNEL drla_lstm_tail_fwd(const float*, const float*, float*, float*,
-                               float*, float, long long, int);
+                               float*, float, long long, int, float*);
 DRLA_KERNEL drla_lstm_tail_bwd(const float*, const float*, const float*,
                                const float*, const float*, float*, float*,
                                long long, int, long long);
 DRLA_KERNEL drla_lstm_tail_fwd_bf16(const bf16raw*, const float*, float*,
-                                    float*, float*, float, long long, int);
+                                    float*, float*, float, long long, int,
+                                    float*);
 DRLA_KERNEL drla_lstm_tail_bwd_bf16(const float*, const float*, const float*,
                                     const float*, const float*, bf16raw*,
                                     float*, long long, int, long long);
@@ -102,11 +103,12 @@ DRLA_KERNEL drla_conv_fwd_l1_c1(const unsigned char*, const bf16raw*,
                                 const bf16raw*, bf16raw*, int,
                                 unsigned char*);
 DRLA_KERNEL drla_conv_fwd_l2(const bf16raw*, const bf16raw*, const bf16raw*,
-                             bf16raw*, int);
+                             bf16raw*, int, long long);
 DRLA_KERNEL drla_conv_fwd_l3(const bf16raw*, const bf16raw*, const bf16raw*,
-                             bf16raw*, int);
+                             bf16raw*, int, long long);
 DRLA_KERNEL drla_relu_mask_bwd(const bf16raw*, const bf16raw*, bf16raw*,
-                               float*, long long, int, long long, long long);
+                               float*, long long, int, long long, long long,
+                               long long);
 DRLA_KERNEL drla_wgrad_finalize(float*, bf16raw*, int, int, float*,
                                 bf16raw*);
 DRLA_KERNEL drla_conv_wgrad_l1(const unsigned char*, const bf16raw*, float*,
@@ -175,7 +177,7 @@ DRLA_KERNEL drla_mlp_heads_fwd(
     const float*, const bf16raw*, const bf16raw*, const bf16raw*,
     const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
     const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
-    const bf16raw*, bf16raw*, float*, bf16raw*, int, int);
+    const bf16raw*, bf16raw*, float*, bf16raw*, int, int, bf16raw*, float*);
 DRLA_KERNEL drla_mlp_heads_bwd(
     const bf16raw*, const float*, const bf16raw*, const bf16raw*,
     const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
@@ -192,11 +194,14 @@ DRLA_KERNEL drla_heads_wgrad(
     bf16raw*, bf16raw*, bf16raw*, bf16raw*, bf16raw*, int, int);
 DRLA_KERNEL drla_embed_mlp_fwd(const long long*, const bf16raw*,
                                const bf16raw*, const bf16raw*,
-                               const bf16raw*, bf16raw*, bf16raw*, int, int);
+                               const bf16raw*, bf16raw*, bf16raw*, int, int,
+                               long long*, bf16raw*, long long, const float*,
+                               int);
 DRLA_KERNEL drla_embed_w2t_pack(const bf16raw*, bf16raw*);
 DRLA_KERNEL drla_embed_mlp_bwd(const bf16raw*, long long, const bf16raw*,
                                const bf16raw*, const bf16raw*, bf16raw*,
-                               bf16raw*, float*, int);
+                               bf16raw*, float*, int, const long long*,
+                               float*, int, long long);
 DRLA_KERNEL drla_embed_finalize(float*, bf16raw*, bf16raw*, bf16raw*,
                                 long long);
 

@@ -20,7 +20,8 @@ extern "C" __global__ void drla_lstm_tail_fwd(
     const float* __restrict__ gates, const float* __restrict__ c_prev,
     float* __restrict__ new_h, float* __restrict__ new_c,
     float* __restrict__ stash,  // [N,4H] activated gates (i,g,f,o)
-    float forget_bias, long long N, int H) {
+    float forget_bias, long long N, int H,
+    float* __restrict__ c_stash) {  // [N,H] copy of c_prev (nullable)
   long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   const long long total = N * H;
   const long long stride = gridDim.x * (long long)blockDim.x;
@@ -32,7 +33,9 @@ extern "C" __global__ void drla_lstm_tail_fwd(
     const float g_t = tanhf(gates[g0 + H]);
     const float f_s = drla_sigmoid(gates[g0 + 2 * H] + forget_bias);
     const float o_s = drla_sigmoid(gates[g0 + 3 * H]);
-    const float c_new = f_s * c_prev[idx] + i_s * g_t;
+    const float c_in = c_prev[idx];
+    if (c_stash) c_stash[idx] = c_in;
+    const float c_new = f_s * c_in + i_s * g_t;
     new_c[idx] = c_new;
     new_h[idx] = o_s * tanhf(c_new);
     stash[g0] = i_s;
@@ -85,7 +88,8 @@ extern "C" __global__ void drla_lstm_tail_fwd_bf16(
     const unsigned short* __restrict__ gates,
     const float* __restrict__ c_prev, float* __restrict__ new_h,
     float* __restrict__ new_c, float* __restrict__ stash, float forget_bias,
-    long long N, int H) {
+    long long N, int H,
+    float* __restrict__ c_stash) {  // [N,H] copy of c_prev (nullable)
   long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   const long long total = N * H;
   const long long stride = gridDim.x * (long long)blockDim.x;
@@ -98,7 +102,9 @@ extern "C" __global__ void drla_lstm_tail_fwd_bf16(
     const float f_s = drla_sigmoid(lstm_b2f(gates[g0 + 2 * H])
                                    + forget_bias);
     const float o_s = drla_sigmoid(lstm_b2f(gates[g0 + 3 * H]));
-    const float c_new = f_s * c_prev[idx] + i_s * g_t;
+    const float c_in = c_prev[idx];
+    if (c_stash) c_stash[idx] = c_in;
+    const float c_new = f_s * c_in + i_s * g_t;
     new_c[idx] = c_new;
     new_h[idx] = o_s * tanhf(c_new);
     stash[g0] = i_s;

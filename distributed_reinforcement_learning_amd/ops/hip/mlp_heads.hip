@@ -140,6 +140,29 @@ __device__ void mh_pass(const bf16raw (*act_in)[MH_LD],
   __syncthreads();
 }
 
+// Transposed-weight side output of the forward kernels: the backward dgrad
+// chains want W^T, and the weights do not change between a step's forward
+// and backward, so the forward (which streams every W anyway) emits it and
+// the separate pack launch disappears. One "unit" is 8 consecutive k of one
+// W row: a 16 B load, then 8 stores that are coalesced across the lanes
+// (consecutive lanes = consecutive rows r = consecutive out columns).
+// Units u in [0, 8192) cover one [256,256] matrix exactly once.
+__device__ __forceinline__ void mh_wt_unit(const bf16raw* __restrict__ w,
+                                           bf16raw* __restrict__ out,
+                                           int u) {
+  const int r = u & 255;
+  const int k0 = (u >> 8) * 8;
+  const bf16x8 v = *reinterpret_cast<const bf16x8*>(w + r * 256 + k0);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) out[(k0 + j) * 256 + r] = (bf16raw)v[j];
+}
+
+// wt_pack != null: additionally write the packed transposed weights in the
+// drla_heads_wt_pack layout (below), each block its own share (thread gt of
+// nt strides over the units, so no element is written twice).
+// ws != null: zero the backward's f32 workspace ([N,256] dh ++ 4*256+A+1
+// bias partials) — policy block x its own 16 dh rows, block (0,0) the tail —
+// so the backward needs no fill launch in front of its atomics.
 extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
     const float* __restrict__ h,        // [N,256]
     const bf16raw* __restrict__ W1p, const bf16raw* __restrict__ b1p,
@@ -151,7 +174,9 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
     bf16raw* __restrict__ logits,       // [N,A]
     float* __restrict__ value,          // [N]
     bf16raw* __restrict__ stash,    // [N,5*256]: a1p,a2p,a1v,a2v,h_bf16
-    int N, int A) {
+    int N, int A,
+    bf16raw* __restrict__ wt_pack,  // [270592] (nullable)
+    float* __restrict__ ws) {       // [N*256 + 4*256 + A + 1] (nullable)
   // grid: (ceil(N/16), 2) — blockIdx.y 0 = policy chain, 1 = value chain
   __shared__ bf16raw hb[MH_BM][MH_LD];
   __shared__ bf16raw acta[MH_BM][MH_LD];
@@ -161,6 +186,46 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
   const int row0 = blockIdx.x * MH_BM;
   const bool policy = blockIdx.y == 0;
   const long long soff = (long long)N * MH_HID;
+
+  if (wt_pack) {
+    const int gt = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid;
+    const int nt = gridDim.x * gridDim.y * 256;
+    // four [256,256] transposes: wT1p@0, wT2p@65536, wT1v@139264,
+    // wT2v@204800
+    for (int u = gt; u < 4 * 8192; u += nt) {
+      const int m = u >> 13;
+      const bf16raw* w = (m == 0) ? W1p : (m == 1) ? W2p
+                       : (m == 2) ? W1v : W2v;
+      const int off = (m == 0) ? 0 : (m == 1) ? 65536
+                    : (m == 2) ? 139264 : 204800;
+      mh_wt_unit(w, wt_pack + off, u & 8191);
+    }
+    // wT3p [256,32] @131072 (cols >= A zero), W3v copy @270336
+    for (int e = gt; e < 8192 + 256; e += nt) {
+      if (e < 8192) {
+        const int c = e & 31;
+        wt_pack[131072 + e] =
+            (c < A) ? W3p[c * 256 + (e >> 5)] : (bf16raw)0;
+      } else {
+        wt_pack[270336 + (e - 8192)] = W3v[e - 8192];
+      }
+    }
+  }
+  if (ws && policy) {
+    const int r = tid >> 4;
+    const int c0 = (tid & 15) * 16;
+    const int grow = row0 + r;
+    if (grow < N) {
+      float4* p = reinterpret_cast<float4*>(
+          ws + (long long)grow * MH_HID + c0);
+      const float4 z4 = {0.f, 0.f, 0.f, 0.f};
+      p[0] = z4; p[1] = z4; p[2] = z4; p[3] = z4;
+    }
+    if (blockIdx.x == 0) {
+      const int tail = 4 * MH_HID + A + 1;
+      for (int i = tid; i < tail; i += 256) ws[soff + i] = 0.0f;
+    }
+  }
 
   // load h (f32 -> bf16); the policy block stashes the bf16 copy
   {
@@ -535,7 +600,17 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_fwd(
     const bf16raw* __restrict__ b2,       // [256]
     bf16raw* __restrict__ out,            // [N,256] (post-ReLU2)
     bf16raw* __restrict__ a1stash,        // [N,256] (post-ReLU1)
-    int N, int A) {
+    int N, int A,
+    long long* __restrict__ idx_stash,    // [N] clamped pa copy (nullable)
+    bf16raw* __restrict__ w2t,            // [256,256] W2^T out (nullable)
+    long long slab_stride,                // 0: out is [N,256] contiguous
+    const float* __restrict__ h_src,      // [N,H] f32 (slab mode)
+    int H) {
+  // slab mode (slab_stride != 0): out points at the embedding columns of a
+  // row-major [N, slab_stride] bf16 slab — the gate-GEMM input, assembled in
+  // place. The block's 16 rows also get h (f32 -> bf16, the rounding of
+  // .to(bf16)) in the H columns after the embedding and the 8 pad columns
+  // (1, 0 x 7) after those; 16 B stores, H % 8 == 0.
   __shared__ bf16raw a1img[MH_BM][MH_LD];
   __shared__ bf16raw outimg[MH_BM][MH_LD];
   const int tid = threadIdx.x;
@@ -548,6 +623,8 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_fwd(
     // index must not become an aperture fault (drla_common.h)
     const long long idx =
         (grow < N) ? drla_clamp_idx((int)pa[grow], A) : 0;
+    // the backward scatter reads this copy, never the caller's buffer
+    if (idx_stash && grow < N && (tid & 15) == 0) idx_stash[grow] = idx;
     const bf16raw* trow = table + idx * MH_HID + c0;
     for (int c = 0; c < 16; ++c) {
       const float v =
@@ -559,7 +636,49 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_fwd(
   }
   __syncthreads();
   mh_pass<true, false>(a1img, outimg, W2, b2, nullptr, nullptr, nullptr,
-                       out, nullptr, row0, N, MH_HID, MH_HID);
+                       slab_stride ? nullptr : out, nullptr, row0, N, MH_HID,
+                       MH_HID);
+  // the side outputs come AFTER the pass: nothing of theirs is live while
+  // the pass holds its weight fragments (VGPR budget / occupancy)
+  if (slab_stride != 0) {
+    const int r = tid >> 4;
+    const int c0 = (tid & 15) * 16;
+    const int grow = row0 + r;
+    if (grow < N) {
+      // the post-ReLU2 image mh_pass left in LDS -> the slab's embedding
+      // columns, two 16 B stores per thread (mh_pass ends on a barrier)
+      bf16raw* orow = out + (long long)grow * slab_stride;
+      *reinterpret_cast<uint4*>(orow + c0) =
+          *reinterpret_cast<const uint4*>(&outimg[r][c0]);
+      *reinterpret_cast<uint4*>(orow + c0 + 8) =
+          *reinterpret_cast<const uint4*>(&outimg[r][c0 + 8]);
+      // h (f32 -> bf16) and the pad columns behind it
+      bf16raw* hrow = orow + MH_HID;
+#pragma unroll 1  // short trip count; unrolled it costs VGPRs
+      for (int c = (tid & 15) * 8; c < H; c += 128) {
+        const float4 v0 = *reinterpret_cast<const float4*>(
+            h_src + (long long)grow * H + c);
+        const float4 v1 = *reinterpret_cast<const float4*>(
+            h_src + (long long)grow * H + c + 4);
+        uint4 p;
+        p.x = drla_f32x2_to_bf16x2(v0.x, v0.y);
+        p.y = drla_f32x2_to_bf16x2(v0.z, v0.w);
+        p.z = drla_f32x2_to_bf16x2(v1.x, v1.y);
+        p.w = drla_f32x2_to_bf16x2(v1.z, v1.w);
+        *reinterpret_cast<uint4*>(hrow + c) = p;
+      }
+      if ((tid & 15) == 0) {
+        // bf16 1.0 = 0x3F80 in column 0, zeros in columns 1..7
+        *reinterpret_cast<uint4*>(hrow + H) = uint4{0x3F80u, 0u, 0u, 0u};
+      }
+    }
+  }
+  if (w2t) {
+    // W2^T for the backward's dgrad pass, each block its share of the units
+    for (int u = blockIdx.x * 256 + tid; u < 8192; u += gridDim.x * 256) {
+      mh_wt_unit(W2, w2t, u);
+    }
+  }
 }
 
 // [256,256] transpose pack for the dgrad pass below
@@ -580,13 +699,23 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
     const bf16raw* __restrict__ out, const bf16raw* __restrict__ a1stash,
     const bf16raw* __restrict__ W2T,  // [256,256] pre-transposed
     bf16raw* __restrict__ dz2,        // [N,256]
-    bf16raw* __restrict__ da1,        // [N,256]
-    float* __restrict__ bias_ws, int N) {
+    bf16raw* __restrict__ da1,        // [N,256] (null with scat_idx)
+    float* __restrict__ bias_ws, int N,
+    const long long* __restrict__ scat_idx,  // [N] table rows (nullable)
+    float* __restrict__ scat,                // [A,256] f32 table-grad sums
+    int A,
+    long long out_stride) {  // elements between rows of out (256: packed;
+                             // wider: out lives in the xh slab)
   __shared__ bf16raw dz2img[MH_BM][MH_LD];
   __shared__ bf16raw da1img[MH_BM][MH_LD];
   __shared__ float colsum[MH_HID];
+  __shared__ int srow[MH_BM];
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * MH_BM;
+  if (scat_idx && tid < MH_BM) {
+    srow[tid] = (row0 + tid < N)
+        ? drla_clamp_idx((int)scat_idx[row0 + tid], A) : -1;
+  }
   if (tid < MH_HID) colsum[tid] = 0.0f;
   __syncthreads();
   {
@@ -598,7 +727,7 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
       float v = 0.0f;
       if (grow < N) {
         const float o =
-            mh_b2f(out[(long long)grow * MH_HID + c0 + c]);
+            mh_b2f(out[(long long)grow * out_stride + c0 + c]);
         if (o > 0.0f) {
           v = mh_b2f(dy[(long long)grow * dy_stride + c0 + c]);
         }
@@ -620,6 +749,29 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
   mh_pass<false, false>(dz2img, da1img, W2T, nullptr, a1stash, da1,
                         colsum, nullptr, nullptr, row0, N, MH_HID, MH_HID);
   if (tid < MH_HID) atomicAdd(&bias_ws[tid], colsum[tid]);
+  if (scat_idx) {
+    // table scatter in the epilogue (was drla_embed_bwd_scatter re-reading
+    // da1 from global one launch later): thread = column, walking the
+    // block's rows of the bf16 da1 image mh_pass left in LDS. Runs of rows
+    // with the same table row are summed first, so a block issues between
+    // 1 and MH_BM atomics per column, coalesced across the lanes. The
+    // addends are the bf16-rounded values the standalone scatter reads.
+    const int oc = tid;  // blockDim.x == MH_HID
+    float acc = 0.0f;
+    int cur = -1;
+#pragma unroll 1  // unrolled, the 16 row/value pairs cost VGPRs (occupancy)
+    for (int r = 0; r < MH_BM; ++r) {
+      const int row = srow[r];
+      if (row < 0) break;  // rows past N (only at the block's end)
+      if (row != cur) {
+        if (cur >= 0) atomicAdd(&scat[(long long)cur * MH_HID + oc], acc);
+        acc = 0.0f;
+        cur = row;
+      }
+      acc += mh_b2f(da1img[r][oc]);
+    }
+    if (cur >= 0) atomicAdd(&scat[(long long)cur * MH_HID + oc], acc);
+  }
 }
 
 // finalize for the fused embed backward: cast the persistent f32 scratch

@@ -23,7 +23,19 @@ __device__ __forceinline__ float vt_ld(const bf16raw* p, long long i) {
   return __uint_as_float(x);
 }
 
-// grid = B blocks of 256; losses[4] must be ZERO on entry (atomicAdd).
+// grid = B blocks of 256.
+// Loss reduction, two modes:
+//   partials == null: one atomicAdd quadruple per block; losses[4] must be
+//     ZERO on entry.
+//   partials != null: block b stores its (pi, base, ent, total) partial to
+//     partials[b*4..], fences and takes a ticket on *counter; the block that
+//     draws the last ticket sums the B partials IN BLOCK ORDER, writes
+//     losses[0..3] and resets the counter. Nothing has to be zero on entry
+//     except the counter (zeroed once at allocation, restored by every
+//     launch), and the sums are run-to-run deterministic. One launch at a
+//     time may use a given (partials, counter) pair.
+// act_stash != null: the block copies its actions row out, so a backward
+// that runs after the caller's actions buffer was rewritten reads the copy.
 // T <= VT_MAX_T (drla_common.h; the launcher checks it): it sizes the LDS
 // scan buffers below.
 // Reward clipping (clip_mode: 0 = abs_one, 1 = soft_asymmetric, 2 = none,
@@ -46,12 +58,17 @@ void drla_vtrace_loss_fwd(
     float* __restrict__ vs_stash,              // [B,T-2]
     float* __restrict__ adv_stash,             // [B,T-2]
     float* __restrict__ losses,                // [4]: pi, base, ent, total
-    int B, int T, int A) {
+    int B, int T, int A,
+    float* __restrict__ partials,              // [>=B,4] (nullable)
+    unsigned int* __restrict__ counter,        // [1] (with partials)
+    int* __restrict__ act_stash) {             // [B,T] (nullable)
   __shared__ float rho[VT_MAX_T];
   __shared__ float vsm[VT_MAX_T];
   __shared__ float rc[VT_MAX_T];
   __shared__ float gc[VT_MAX_T];
   __shared__ float red[3 * 4];
+  __shared__ int is_last;
+  __shared__ float stage[256];  // last block: one chunk of the partials
 
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -95,7 +112,9 @@ void drla_vtrace_loss_fwd(
                                   : logits_f32[base + k];
       p_stash[base + k] = __expf(x - mx) * inv;
     }
-    const int a = drla_clamp_idx(actions[row + t], A);
+    const int a_raw = actions[row + t];
+    if (act_stash) act_stash[row + t] = a_raw;
+    const int a = drla_clamp_idx(a_raw, A);
     rho[t] = p_stash[base + a] / mu[base + a];
   }
   __syncthreads();
@@ -166,11 +185,46 @@ void drla_vtrace_loss_fwd(
       s1 += red[4 + w];
       s2 += red[8 + w];
     }
-    atomicAdd(&losses[0], s0);
-    atomicAdd(&losses[1], s1);
-    atomicAdd(&losses[2], s2);
-    atomicAdd(&losses[3], s0 + c_bl * s1 + c_ent * s2);
+    if (!partials) {
+      atomicAdd(&losses[0], s0);
+      atomicAdd(&losses[1], s1);
+      atomicAdd(&losses[2], s2);
+      atomicAdd(&losses[3], s0 + c_bl * s1 + c_ent * s2);
+    } else {
+      partials[b * 4 + 0] = s0;
+      partials[b * 4 + 1] = s1;
+      partials[b * 4 + 2] = s2;
+      partials[b * 4 + 3] = s0 + c_bl * s1 + c_ent * s2;
+      __threadfence();  // partial visible device-wide before the ticket
+      const unsigned int ticket = atomicAdd(counter, 1u);
+      is_last = (ticket == (unsigned int)(B - 1));
+    }
   }
+  if (!partials) return;
+  __syncthreads();
+  if (!is_last) return;  // block-uniform (LDS flag)
+  __threadfence();
+  // the whole block fetches the partials (one load each, in flight
+  // together — a single thread walking them pays B serial L2 round trips),
+  // then 4 threads add their column up in block order from LDS.
+  // Device-scope loads: the other blocks' partials must not come from this
+  // CU's vector cache.
+  float s = 0.0f;
+  for (int base = 0; base < B * 4; base += 256) {
+    const int i = base + tid;
+    stage[tid] = (i < B * 4)
+        ? __hip_atomic_load(&partials[i], __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT)
+        : 0.0f;
+    __syncthreads();
+    if (tid < 4) {
+      const int nb = min(64, B - base / 4);
+      for (int j = 0; j < nb; ++j) s += stage[j * 4 + tid];
+    }
+    __syncthreads();
+  }
+  if (tid < 4) losses[tid] = s;
+  if (tid == 0) *counter = 0u;  // next launch starts from a clean ticket
 }
 
 // one thread per (b,t): writes the full A-row of dlogits + dvalue.

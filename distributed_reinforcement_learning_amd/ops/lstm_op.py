@@ -15,6 +15,7 @@ from typing import Tuple
 import torch
 
 from distributed_reinforcement_learning_amd import ops as _ops
+from distributed_reinforcement_learning_amd.ops import conv_op
 
 # largest hidden size the LSTM sequence kernels take (ops/hip/drla_common.h
 # LSTM_SEQ_MAX_HIDDEN); the launchers refuse anything wider
@@ -28,10 +29,14 @@ class _FusedLstmTail(torch.autograd.Function):
         ext = _ops.require_ext()
         # bf16 gates (straight from the addmm) are consumed natively —
         # no [N,4H] f32 cast on either side of the tail
-        new_h, new_c, stash = ext.lstm_tail_fwd(gates.contiguous(),
-                                                c_prev.contiguous(),
-                                                forget_bias)
-        ctx.save_for_backward(stash, c_prev, new_c)
+        # STASH_INPUTS (graphed step): the kernel copies c_prev out and the
+        # backward's df = d_tc * c_prev reads the copy, not the caller's
+        # buffer (it may be rewritten between forward and backward)
+        stash_c = conv_op.STASH_INPUTS
+        res = ext.lstm_tail_fwd(gates.contiguous(), c_prev.contiguous(),
+                                forget_bias, stash_c=stash_c)
+        new_h, new_c, stash = res[:3]
+        ctx.save_for_backward(stash, res[3] if stash_c else c_prev, new_c)
         ctx.bf16_gates = gates.dtype == torch.bfloat16
         # no materialized grad_c: the batched unroll consumes only new_h,
         # so autograd would otherwise zero-fill a [N,H] every step

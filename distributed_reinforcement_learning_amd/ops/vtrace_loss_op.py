@@ -16,6 +16,7 @@ from typing import Tuple
 import torch
 
 from distributed_reinforcement_learning_amd import ops as _ops
+from distributed_reinforcement_learning_amd.ops import conv_op
 
 _CLIP_MODE = {"abs_one": 0, "soft_asymmetric": 1, "none": 2}
 
@@ -27,12 +28,21 @@ class _FusedVtraceLoss(torch.autograd.Function):
                 rewards: torch.Tensor, done: torch.Tensor, gamma: float,
                 clip_mode: int, c_bl: float, c_ent: float):
         ext = _ops.require_ext()
-        losses, p_stash, vs_stash, adv_stash = ext.vtrace_loss_fwd(
+        # nofill: fixed-order ticketed loss sums, no zero-fill launch.
+        # STASH_INPUTS (graphed step): the kernel copies actions out and the
+        # backward reads the copy — the caller's buffer may be rewritten
+        # between forward and backward (runtime/graphed.py)
+        stash = conv_op.STASH_INPUTS
+        actions = actions.contiguous()
+        res = ext.vtrace_loss_fwd(
             logits.contiguous(), value.contiguous(), mu.contiguous(),
-            actions.contiguous(), rewards.contiguous(), done.contiguous(),
-            gamma, clip_mode, c_bl, c_ent)
+            actions, rewards.contiguous(), done.contiguous(),
+            gamma, clip_mode, c_bl, c_ent, nofill=True,
+            stash_actions=stash)
+        losses, p_stash, vs_stash, adv_stash = res[:4]
         ctx.save_for_backward(p_stash, vs_stash, adv_stash,
-                              value.contiguous(), actions.contiguous())
+                              value.contiguous(),
+                              res[4] if stash else actions)
         ctx.want_bf16 = logits.dtype == torch.bfloat16
         ctx.coefs = (c_bl, c_ent)
         ctx.set_materialize_grads(False)

@@ -21,9 +21,14 @@ Step structure (three graphs + a copy stream):
   copy str: the NEXT batch's pinned -> static-input H2D, ordered after
             graph 1 via an event, so the ~18 MB upload hides behind the
             backward. Every read of a static input happens INSIDE graph 1:
-            the conv-l1 kernel stashes its u8 input in passing and the
-            other backward-read inputs (previous_action / action /
-            initial_c) are cloned at the top of the forward
+            each forward kernel that reads a backward-read input (conv-l1:
+            state; embed MLP: previous_action; LSTM tail: initial_c;
+            V-trace loss: action) stashes a copy in passing, no clone
+            launches. The embed and heads forwards also emit the W^T their
+            backwards need and the heads forward zeroes the backward's
+            atomics workspace, so graph 2 starts without pack or fill
+            launches; the V-trace loss sums take no zero-fill either
+            (ticketed fixed-order reduction)
   graph 2:  backward (autograd ASSIGNS scatter-mode grads — no
             AccumulateGrad adds)
   graph 3:  one-kernel grad gather + (world > 1: CAPTURED RCCL all-reduce)
@@ -37,7 +42,6 @@ graph 3 are shared with the other learners: runtime/_capture.py.
 
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -99,8 +103,8 @@ class GraphedImpalaStep(CapturedStep):
         # forward and backward are SEPARATE graphs so the next step's H2D
         # upload (pinned -> static inputs, ~110 us) can overlap the
         # backward on a copy stream; _fwd() confines every input read to
-        # graph 1 (conv-l1 input stash + clones of the backward-read
-        # fields), so the overlap cannot tear the backward's reads.
+        # graph 1 (in-kernel stashes of the backward-read fields), so the
+        # overlap cannot tear the backward's reads.
         self.g_fwd = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fwd):
             self._total, self.losses = self._fwd()
@@ -123,19 +127,15 @@ class GraphedImpalaStep(CapturedStep):
 
     def _fwd(self):
         agent = self.agent
-        i = dict(self.inputs)
+        i = self.inputs
         # The overlapped H2D upload (copy stream) is ordered only after
-        # the FORWARD, but four inputs are re-read by backward kernels
-        # (conv-l1 wgrad: state; embed scatter: previous_action; V-trace
-        # bwd: action; LSTM tail bwd: initial_c) — clone those INSIDE the
-        # forward graph so every read of a static buffer happens before
-        # the upload barrier. ~19 MB through the capture pool, ~6 us.
-        # (state is NOT cloned: the conv-l1 forward kernel bundles a
-        # pass-through stash of its input instead — ops/conv_op.py
-        # STASH_INPUTS, ~4 us bundled vs ~20 us standalone clone)
-        if os.environ.get("DRLA_NO_INPUT_CLONE") != "1":  # measurement-only escape
-            for k in ("previous_action", "action", "initial_c"):
-                i[k] = i[k].clone()
+        # the FORWARD, but four inputs feed backward kernels (conv-l1
+        # wgrad: state; embed scatter: previous_action; V-trace bwd:
+        # action; LSTM tail bwd: initial_c). Under conv_op.STASH_INPUTS
+        # the forward kernel that reads each of them writes a copy in
+        # passing and the backward consumes that copy, so every read of a
+        # static buffer happens before the upload barrier without a clone
+        # launch (a wrapper on a non-fused fallback clones for itself).
         s = agent.prepare_frames(i["state"])
         pi_loss, baseline_loss, entropy, total = agent.compute_losses(
             s, i["reward"], i["action"], i["done"], i["behavior_policy"],
