@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 
 from distributed_reinforcement_learning_amd import ops as _ops
-from distributed_reinforcement_learning_amd.ops import conv_op
+from distributed_reinforcement_learning_amd.ops import conv_op, input_slots
 
 
 class _EmbedLookup(torch.autograd.Function):
@@ -59,9 +59,14 @@ class _FusedActionEmbed(torch.autograd.Function):
         # xh_slab: out is written into (and returned as) the slab's columns
         # [emb_col, emb_col + 256); the kernel also fills bf16(h) and the
         # pad columns behind them (ops/xh_op.py)
+        s_idx, d_idx = input_slots.lookup(idx)
+        s_h, d_h = input_slots.lookup(h)
+        slot = s_idx if s_idx is not None else s_h
         res = ext.embed_mlp_fwd(idx, table, b1, w2, b2, stash_idx=stash,
                                 want_w2t=want_w2t, xh_slab=xh_slab,
-                                emb_col=emb_col, h=h)
+                                emb_col=emb_col, h=h, slot=slot,
+                                slot_dist=([d_idx, d_h] if slot is not None
+                                           else []))
         out, a1 = res[0], res[1]
         ctx.save_for_backward(res[2] if stash else idx, a1, out, w2)
         # an op-made intermediate, valid for this forward's weights

@@ -44,6 +44,20 @@ bf16raw* bf16_ptr(const torch::Tensor& t, const char* name) {
 
 // kernels that take bf16 OR float32 have a pointer pair, one of them null
 struct DualPtr { bf16raw* bf16; float* f32; };
+
+// The device slot word of double-buffered static inputs (drla_slot_base):
+// absent -> null, and the kernel reads its inputs where they are given.
+// dist holds one element distance per slotted input of the launcher.
+const int* slot_ptr(const c10::optional<torch::Tensor>& slot,
+                    const std::vector<int64_t>& dist, size_t n_dist) {
+  if (!slot.has_value()) return nullptr;
+  TORCH_CHECK(slot->is_cuda() && slot->scalar_type() == torch::kInt &&
+                  slot->numel() == 1,
+              "slot must be one int32 on the GPU");
+  TORCH_CHECK(dist.size() == n_dist, "slot_dist needs ", n_dist, " entries");
+  for (auto d : dist) TORCH_CHECK(d >= 0, "negative slot distance");
+  return slot->data_ptr<int>();
+}
 DualPtr dual_ptr(const torch::Tensor& t) {
   if (t.scalar_type() == torch::kBFloat16)
     return {static_cast<bf16raw*>(t.data_ptr()), nullptr};
@@ -151,8 +165,13 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
 
 std::tuple<torch::Tensor, torch::Tensor> conv_fwd(
     int layer, torch::Tensor in, torch::Tensor w, torch::Tensor bias,
-    bool stash_input, c10::optional<torch::Tensor> out_slab) {
+    bool stash_input, c10::optional<torch::Tensor> out_slab,
+    c10::optional<torch::Tensor> slot, std::vector<int64_t> slot_dist) {
   check_gpu_contig(in, "in");
+  TORCH_CHECK(!slot.has_value() || layer < 2,
+              "only the u8 input layers take a slot");
+  const int* slotp = slot_ptr(slot, slot_dist, 1);
+  const long long in_dist = slotp ? slot_dist[0] : 0;
   check_gpu_contig(w, "w");
   check_gpu_contig(bias, "bias");
   const auto& cfg = conv_layer(layer);
@@ -195,7 +214,8 @@ std::tuple<torch::Tensor, torch::Tensor> conv_fwd(
   if (layer <= 1) {
     hipLaunchKernelGGL(kConvFwdU8[layer], grid, dim3(DRLA_CONV_BLOCK), 0,
                        cur_stream(), in.data_ptr<uint8_t>(), BF16P(w),
-                       BF16P(bias), BF16PM(out), batch, stashp);
+                       BF16P(bias), BF16PM(out), batch, stashp, slotp,
+                       in_dist);
   } else {
     hipLaunchKernelGGL(kConvFwdBf16[layer - 2], grid, dim3(DRLA_CONV_BLOCK),
                        0, cur_stream(), BF16P(in), BF16P(w), BF16P(bias),
@@ -667,11 +687,30 @@ torch::Tensor embed_bwd(torch::Tensor indices, torch::Tensor grad_out,
   return out;
 }
 
+// One launch for the graphed IMPALA step's per-step host write: the learning
+// rate and the input set the coming replay reads (runtime/graphed.py).
+void set_lr_slot(torch::Tensor lr_buf, torch::Tensor slot_word, double lr,
+                 int64_t slot) {
+  TORCH_CHECK(lr_buf.is_cuda() && lr_buf.scalar_type() == torch::kFloat &&
+                  lr_buf.numel() == 1, "lr_buf must be one f32 on the GPU");
+  TORCH_CHECK(slot_word.is_cuda() && slot_word.scalar_type() == torch::kInt &&
+                  slot_word.numel() == 1 && (slot == 0 || slot == 1),
+              "slot_word must be one int32 on the GPU, slot 0 or 1");
+  hipLaunchKernelGGL(drla_set_lr_slot, dim3(1), dim3(64), 0, cur_stream(),
+                     lr_buf.data_ptr<float>(), slot_word.data_ptr<int>(),
+                     static_cast<float>(lr), (int)slot);
+}
+
 std::vector<torch::Tensor> vtrace_loss_fwd(
     torch::Tensor logits, torch::Tensor value, torch::Tensor mu,
     torch::Tensor actions, torch::Tensor rewards, torch::Tensor done,
     double gamma, int64_t clip_mode, double c_bl, double c_ent,
-    bool nofill, bool stash_actions) {
+    bool nofill, bool stash_actions, c10::optional<torch::Tensor> slot,
+    std::vector<int64_t> slot_dist) {
+  // slot_dist: mu, actions, rewards, done
+  const int* slotp = slot_ptr(slot, slot_dist, 4);
+  const std::vector<int64_t> sd =
+      slotp ? slot_dist : std::vector<int64_t>{0, 0, 0, 0};
   check_all_gpu_contig("vtrace_loss input", logits, value, mu, actions,
                        rewards, done);
   TORCH_CHECK(actions.scalar_type() == torch::kInt, "actions must be int32");
@@ -724,7 +763,8 @@ std::vector<torch::Tensor> vtrace_loss_fwd(
       static_cast<float>(c_ent), p_stash.data_ptr<float>(),
       vs_stash.data_ptr<float>(), adv_stash.data_ptr<float>(),
       losses.data_ptr<float>(), B, T, A, partials_ptr, counter_ptr,
-      act_stash_ptr);
+      act_stash_ptr, slotp, (long long)sd[0], (long long)sd[1],
+      (long long)sd[2], (long long)sd[3]);
   if (stash_actions) return {losses, p_stash, vs_stash, adv_stash, act_stash};
   return {losses, p_stash, vs_stash, adv_stash};
 }
@@ -756,7 +796,10 @@ std::tuple<torch::Tensor, torch::Tensor> vtrace_loss_bwd(
 // backward that must not re-read the caller's c_prev buffer
 std::vector<torch::Tensor> lstm_tail_fwd(
     torch::Tensor gates, torch::Tensor c_prev, double forget_bias,
-    bool stash_c) {
+    bool stash_c, c10::optional<torch::Tensor> slot,
+    std::vector<int64_t> slot_dist) {
+  const int* slotp = slot_ptr(slot, slot_dist, 1);
+  const long long c_dist = slotp ? slot_dist[0] : 0;
   check_gpu_contig(gates, "gates");
   check_gpu_contig(c_prev, "c_prev");
   const bool bf16 = gates.scalar_type() == torch::kBFloat16;
@@ -783,14 +826,16 @@ std::vector<torch::Tensor> lstm_tail_fwd(
                        dim3(DRLA_BLOCK), 0, cur_stream(), BF16P(gates),
                        c_prev.data_ptr<float>(), new_h.data_ptr<float>(),
                        new_c.data_ptr<float>(), stash.data_ptr<float>(),
-                       static_cast<float>(forget_bias), N, H, c_stash_ptr);
+                       static_cast<float>(forget_bias), N, H, c_stash_ptr,
+                       slotp, c_dist);
   } else {
     hipLaunchKernelGGL(drla_lstm_tail_fwd, dim3(drla_grid(N * H)),
                        dim3(DRLA_BLOCK), 0, cur_stream(),
                        gates.data_ptr<float>(), c_prev.data_ptr<float>(),
                        new_h.data_ptr<float>(), new_c.data_ptr<float>(),
                        stash.data_ptr<float>(),
-                       static_cast<float>(forget_bias), N, H, c_stash_ptr);
+                       static_cast<float>(forget_bias), N, H, c_stash_ptr,
+                       slotp, c_dist);
   }
   if (stash_c) return {new_h, new_c, stash, c_stash};
   return {new_h, new_c, stash};
@@ -939,7 +984,12 @@ std::vector<torch::Tensor> embed_mlp_fwd(
     torch::Tensor pa, torch::Tensor table, torch::Tensor b1,
     torch::Tensor w2, torch::Tensor b2, bool stash_idx, bool want_w2t,
     c10::optional<torch::Tensor> xh_slab, int64_t emb_col,
-    c10::optional<torch::Tensor> h_opt) {
+    c10::optional<torch::Tensor> h_opt, c10::optional<torch::Tensor> slot,
+    std::vector<int64_t> slot_dist) {
+  // slot_dist: pa, h (0 for an input that is not double-buffered)
+  const int* slotp = slot_ptr(slot, slot_dist, 2);
+  const long long pa_dist = slotp ? slot_dist[0] : 0;
+  const long long h_dist = slotp ? slot_dist[1] : 0;
   check_all_gpu_contig("embed fwd input", pa, table, b1, w2, b2);
   TORCH_CHECK(pa.scalar_type() == torch::kLong, "pa must be int64");
   const int N = pa.numel();
@@ -988,7 +1038,7 @@ std::vector<torch::Tensor> embed_mlp_fwd(
                      cur_stream(), i64p(pa), BF16P(table), BF16P(b1),
                      BF16P(w2), BF16P(b2), BF16PM(out), BF16PM(a1), N,
                      (int)table.size(0), idx_ptr, w2t_ptr, slab_stride, h_ptr,
-                     H);
+                     H, slotp, pa_dist, h_dist);
   return res;
 }
 
@@ -1374,6 +1424,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("normalize_frames_bf16", &normalize_frames_bf16,
         "uint8 frames -> bf16/255 (K11)");
   m.def("vtrace_scan", &vtrace_scan, "fused V-trace reverse scan (K5)");
+  // underscore: a helper of runtime/graphed.py, not part of the op surface
+  m.def("_set_lr_slot", &set_lr_slot,
+        "write the learning rate and the input-slot word in one launch");
   m.def("vtrace_loss_fwd", &vtrace_loss_fwd,
         "fused IMPALA loss pipeline forward (K5+K7+K13); nofill: ticketed "
         "fixed-order loss sums, no zero-fill; stash_actions: also returns "
@@ -1382,14 +1435,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("actions"), py::arg("rewards"), py::arg("done"),
         py::arg("gamma"), py::arg("clip_mode"), py::arg("c_bl"),
         py::arg("c_ent"), py::arg("nofill") = false,
-        py::arg("stash_actions") = false);
+        py::arg("stash_actions") = false, py::arg("slot") = py::none(),
+        py::arg("slot_dist") = std::vector<int64_t>{});
   m.def("vtrace_loss_bwd", &vtrace_loss_bwd,
         "fused IMPALA loss pipeline backward (closed form)");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("conv_fwd", &conv_fwd,
         "MFMA implicit-GEMM conv fwd, fused normalize+bias+ReLU (K1)",
         py::arg("layer"), py::arg("x"), py::arg("w"), py::arg("bias"),
-        py::arg("stash_input"), py::arg("out_slab") = py::none());
+        py::arg("stash_input"), py::arg("out_slab") = py::none(),
+        py::arg("slot") = py::none(),
+        py::arg("slot_dist") = std::vector<int64_t>{});
   m.def("conv_wgrad", &conv_wgrad, "MFMA conv weight gradient (K1 bwd)");
   m.def("conv_dgrad", &conv_dgrad, "MFMA conv data gradient (K1 bwd)");
   m.def("relu_mask_bwd", &relu_mask_bwd,
@@ -1424,7 +1480,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "action-embedding table gradient (K2 backward)");
   m.def("lstm_tail_fwd", &lstm_tail_fwd, "fused LSTM gate tail fwd (K3)",
         py::arg("gates"), py::arg("c_prev"), py::arg("forget_bias"),
-        py::arg("stash_c") = false);
+        py::arg("stash_c") = false, py::arg("slot") = py::none(),
+        py::arg("slot_dist") = std::vector<int64_t>{});
   m.def("lstm_tail_bwd", &lstm_tail_bwd, "fused LSTM gate tail bwd (K3)");
   m.def("mlp_heads_fwd", &mlp_heads_fwd,
         "fused policy+value MLP heads forward (K4)",
@@ -1439,7 +1496,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pa"), py::arg("table"), py::arg("b1"), py::arg("w2"),
         py::arg("b2"), py::arg("stash_idx") = false,
         py::arg("want_w2t") = false, py::arg("xh_slab") = py::none(),
-        py::arg("emb_col") = 0, py::arg("h") = py::none());
+        py::arg("emb_col") = 0, py::arg("h") = py::none(),
+        py::arg("slot") = py::none(),
+        py::arg("slot_dist") = std::vector<int64_t>{});
   m.def("embed_mlp_bwd", &embed_mlp_bwd,
         "fused action-embedding MLP backward (K2 bwd)",
         py::arg("dy"), py::arg("out"), py::arg("a1"), py::arg("w2"),

@@ -275,14 +275,18 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
 
 CONV_KERNEL drla_conv_fwd_l1(
     const unsigned char* in, const bf16raw* w, const bf16raw* bias,
-    bf16raw* out, int batch, unsigned char* x_stash) {
+    bf16raw* out, int batch, unsigned char* x_stash, const int* slot,
+    long long in_dist) {
+  in = drla_slot_base(in, slot, in_dist);
   conv_fwd_impl<unsigned char, DRLA_CONV_GEOM(0)>(in, w, bias, out, batch,
                                                   x_stash);
 }
 
 CONV_KERNEL drla_conv_fwd_l1_c1(
     const unsigned char* in, const bf16raw* w, const bf16raw* bias,
-    bf16raw* out, int batch, unsigned char* x_stash) {
+    bf16raw* out, int batch, unsigned char* x_stash, const int* slot,
+    long long in_dist) {
+  in = drla_slot_base(in, slot, in_dist);
   // R2D2's single-channel POMDP frames: CI=1 -> K=64; stage per-tap scalars
   conv_fwd_impl<unsigned char, DRLA_CONV_GEOM(1)>(in, w, bias, out, batch,
                                                   x_stash);

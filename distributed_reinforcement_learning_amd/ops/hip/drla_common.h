@@ -118,6 +118,18 @@ __device__ __forceinline__ int drla_clamp_idx(int a, int n) {
   return a < 0 ? 0 : (a >= n ? n - 1 : a);
 }
 
+// Double-buffered static inputs (runtime/graphed.py): a captured graph has
+// fixed addresses, so a kernel that reads such an input takes the address of
+// set 0, the element distance to set 1 and a device-side slot word (0 or 1)
+// that the host writes before the replay. slot == null: the pointer as given.
+// One uniform load per call; kernels call it once per input, at entry.
+template <typename T>
+__device__ __forceinline__ const T* drla_slot_base(const T* p,
+                                                   const int* slot,
+                                                   long long dist) {
+  return slot ? p + (long long)(*slot != 0) * dist : p;
+}
+
 __device__ __forceinline__ float drla_sigmoid(float x) {
   return 1.0f / (1.0f + __expf(-x));
 }

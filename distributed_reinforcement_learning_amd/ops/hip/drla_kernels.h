@@ -14,6 +14,7 @@
 #define DRLA_KERNEL extern "C" __global__ void
 
 // ---- elementwise.hip ------------------------------------------------------
+DRLA_KERNEL drla_set_lr_slot(float*, int*, float, int);
 DRLA_KERNEL drla_u8_normalize_f32(const uchar4*, float4*, long long);
 DRLA_KERNEL drla_u8_normalize_bf16(const uchar4*, ushort4v*, long long);
 DRLA_KERNEL drla_u8_normalize_f32_tail(const unsigned char*, float*,
@@ -33,7 +34,8 @@ DRLA_KERNEL drla_vtrace_scan(const float*, const float*, const float*,
 DRLA_KERNEL drla_vtrace_loss_fwd(
     const bf16raw*, const float*, const float*, const float*, const int*,
     const float*, const unsigned char*, float, int, float, float, float*,
-    float*, float*, float*, int, int, int, float*, unsigned int*, int*);
+    float*, float*, float*, int, int, int, float*, unsigned int*, int*,
+    const int*, long long, long long, long long, long long);
 DRLA_KERNEL drla_vtrace_loss_bwd(
     const float*, const float*, const float*, const float*, const int*,
     const float*, int, float, float, bf16raw*, float*, float*, int, int,
@@ -41,13 +43,14 @@ DRLA_KERNEL drla_vtrace_loss_bwd(
 
 // ---- lstm_gates.hip -------------------------------------------------------
 DRLA_KERNEL drla_lstm_tail_fwd(const float*, const float*, float*, float*,
-                               float*, float, long long, int, float*);
+                               float*, float, long long, int, float*,
+                               const int*, long long);
 DRLA_KERNEL drla_lstm_tail_bwd(const float*, const float*, const float*,
                                const float*, const float*, float*, float*,
                                long long, int, long long);
 DRLA_KERNEL drla_lstm_tail_fwd_bf16(const bf16raw*, const float*, float*,
                                     float*, float*, float, long long, int,
-                                    float*);
+                                    float*, const int*, long long);
 DRLA_KERNEL drla_lstm_tail_bwd_bf16(const float*, const float*, const float*,
                                     const float*, const float*, bf16raw*,
                                     float*, long long, int, long long);
@@ -98,10 +101,11 @@ DRLA_KERNEL drla_grad_gather(const unsigned long long*, const long long*,
 // ---- conv.hip (layer order = DRLA_CONV_LAYERS) ----------------------------
 DRLA_KERNEL drla_mfma_probe(const bf16raw*, const bf16raw*, float*);
 DRLA_KERNEL drla_conv_fwd_l1(const unsigned char*, const bf16raw*,
-                             const bf16raw*, bf16raw*, int, unsigned char*);
+                             const bf16raw*, bf16raw*, int, unsigned char*,
+                             const int*, long long);
 DRLA_KERNEL drla_conv_fwd_l1_c1(const unsigned char*, const bf16raw*,
                                 const bf16raw*, bf16raw*, int,
-                                unsigned char*);
+                                unsigned char*, const int*, long long);
 DRLA_KERNEL drla_conv_fwd_l2(const bf16raw*, const bf16raw*, const bf16raw*,
                              bf16raw*, int, long long);
 DRLA_KERNEL drla_conv_fwd_l3(const bf16raw*, const bf16raw*, const bf16raw*,
@@ -196,7 +200,7 @@ DRLA_KERNEL drla_embed_mlp_fwd(const long long*, const bf16raw*,
                                const bf16raw*, const bf16raw*,
                                const bf16raw*, bf16raw*, bf16raw*, int, int,
                                long long*, bf16raw*, long long, const float*,
-                               int);
+                               int, const int*, long long, long long);
 DRLA_KERNEL drla_embed_w2t_pack(const bf16raw*, bf16raw*);
 DRLA_KERNEL drla_embed_mlp_bwd(const bf16raw*, long long, const bf16raw*,
                                const bf16raw*, const bf16raw*, bf16raw*,

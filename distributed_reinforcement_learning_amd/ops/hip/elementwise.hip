@@ -92,3 +92,14 @@ extern "C" __global__ void drla_f32_to_bf16_zero_kernel(
     src[i] = 0.0f;
   }
 }
+
+// The graphed IMPALA step's per-step host write: this step's learning rate
+// and the input set its replay reads, in one launch (was one fill).
+extern "C" __global__ void drla_set_lr_slot(float* __restrict__ lr_buf,
+                                            int* __restrict__ slot_word,
+                                            float lr, int slot) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    lr_buf[0] = lr;
+    slot_word[0] = slot;
+  }
+}

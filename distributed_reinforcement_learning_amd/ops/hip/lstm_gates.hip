@@ -21,7 +21,9 @@ extern "C" __global__ void drla_lstm_tail_fwd(
     float* __restrict__ new_h, float* __restrict__ new_c,
     float* __restrict__ stash,  // [N,4H] activated gates (i,g,f,o)
     float forget_bias, long long N, int H,
-    float* __restrict__ c_stash) {  // [N,H] copy of c_prev (nullable)
+    float* __restrict__ c_stash,    // [N,H] copy of c_prev (nullable)
+    const int* __restrict__ slot, long long c_dist) {  // drla_slot_base
+  c_prev = drla_slot_base(c_prev, slot, c_dist);
   long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   const long long total = N * H;
   const long long stride = gridDim.x * (long long)blockDim.x;
@@ -89,7 +91,9 @@ extern "C" __global__ void drla_lstm_tail_fwd_bf16(
     const float* __restrict__ c_prev, float* __restrict__ new_h,
     float* __restrict__ new_c, float* __restrict__ stash, float forget_bias,
     long long N, int H,
-    float* __restrict__ c_stash) {  // [N,H] copy of c_prev (nullable)
+    float* __restrict__ c_stash,    // [N,H] copy of c_prev (nullable)
+    const int* __restrict__ slot, long long c_dist) {  // drla_slot_base
+  c_prev = drla_slot_base(c_prev, slot, c_dist);
   long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   const long long total = N * H;
   const long long stride = gridDim.x * (long long)blockDim.x;

@@ -32,87 +32,162 @@ __device__ __forceinline__ float mh_b2f(bf16raw u) {
 }
 
 // One dense pass: out[r][o] = in[r][:] . M[o][:] (+bias, ReLU / mask),
-// M [nout][kdim] row-major global, kdim and nout multiples of 16 (pad rows
-// of M beyond its true extent must be readable — wrappers pad layer-3
-// operands). act images [MH_BM][MH_LD] bf16.
+// M [nout][kdim] row-major global, kdim = KCH * 32; rows of M at or beyond
+// nout are never read. act images [MH_BM][MH_LD] bf16.
+// Precondition: N >= 1 and nout >= 1. Row and column indices past the end
+// are clamped to N - 1 / nout - 1 for the load and the value dropped
+// afterwards; the launchers never launch an empty grid.
 //
-// MASK_STASH != null: v *= (stash > 0), dz-global write + colsum bias
-// partials (backward layers). BIAS != null: v += bias, RELU applies
-// (forward layers). DH != null: terminal f32 row-grad output (ACCUM adds).
-template <bool RELU, bool ACCUM>
-__device__ void mh_pass(const bf16raw (*act_in)[MH_LD],
-                        bf16raw (*act_out)[MH_LD],
-                        const bf16raw* __restrict__ M,   // [nout][kdim]
-                        const bf16raw* __restrict__ bias,  // [nout] or null
-                        const bf16raw* __restrict__ mask_stash,  // [N,256]
-                        bf16raw* __restrict__ dz_global,         // [N,256]
-                        float* __restrict__ colsum,              // [256]
-                        bf16raw* __restrict__ stash,     // [N,nout] or null
-                        float* __restrict__ dh_global,   // [N,256] or null
-                        int row0, int N, int nout, int kdim) {
-  const int tid = threadIdx.x;
-  const int wave = tid / 64;
-  const int lane = tid % 64;
-  const int out0 = wave * 64;          // this wave's 64 output columns
-  const bool live = out0 < nout;
+// A pass is three steps so that its callers can place the loads:
+//   mh_load      request ALL of a wave's A fragments of the pass (KCH chunks
+//                x 4 sixteen-row operands, 4 VGPRs each: 128 VGPRs at
+//                kdim 256). These kernels run 40-80 workgroups, one per CU at
+//                most, and the weights are cold in every XCD's L2 (the
+//                optimizer has just rewritten them, the W^T pack comes from
+//                other workgroups): with the chunks requested one ahead, each
+//                of the 8 chunks paid a full miss before its four MFMAs. In
+//                flight together, a pass pays one. The weights do not depend
+//                on the activations, so a chained kernel requests the later
+//                passes' fragments before the first pass's MFMAs as well.
+//                The loads are unconditional (a row index past nout is
+//                clamped and the operand zeroed in mh_mma), so nothing
+//                branches between them
+//   mh_load_bias / mh_load_mask
+//                the 16 values per lane the epilogue adds or masks with,
+//                requested with the weights: read in the epilogue, each was
+//                a dependent 2-byte load with its own wait
+//   mh_mma       the MFMAs: k ascending, ni 0..3 per chunk
+//   mh_epilogue  un-transpose, bias / ReLU / mask, side outputs
+//
+// SIDE == MH_MASK: v *= (stash > 0), dz-global write + colsum bias partials
+// (backward layers). SIDE == MH_BIAS: v += bias, RELU applies (forward
+// layers). DH != null: terminal f32 row-grad output, added atomically.
+template <int KCH>
+struct MhFrags {
+  bf16x8 a[KCH][4];
+};
 
-  f32x4 acc[4];
-  for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
+struct MhSide {
+  bf16raw v[4][4];  // [ni][r], the epilogue's (ni, r) walk
+};
 
-  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (live) {
-    // software-pipelined k-loop: the next chunk's global weight fragments
-    // load into registers while this chunk's MFMAs run (the serial
-    // load->mfma chain across ~8 chunks x 3 chained passes is what sets
-    // these kernels' time — 40-80 blocks can't hide it with occupancy)
-    bf16x8 a_cur0, a_cur1, a_cur2, a_cur3;
-    const int kf = (lane >> 4) * 8;
-#define DRLA_MH_LOAD(ni, dst, k0)                                       \
-    {                                                                   \
-      const int orow = out0 + (ni) * 16 + (lane & 15);                  \
-      dst = (orow < nout)                                               \
-          ? *reinterpret_cast<const bf16x8*>(                           \
-                M + (long long)orow * kdim + (k0) + kf)                 \
-          : zero8;                                                      \
-    }
-    DRLA_MH_LOAD(0, a_cur0, 0); DRLA_MH_LOAD(1, a_cur1, 0);
-    DRLA_MH_LOAD(2, a_cur2, 0); DRLA_MH_LOAD(3, a_cur3, 0);
-    for (int k0 = 0; k0 < kdim; k0 += 32) {
-      bf16x8 a_nxt0, a_nxt1, a_nxt2, a_nxt3;
-      if (k0 + 32 < kdim) {
-        DRLA_MH_LOAD(0, a_nxt0, k0 + 32); DRLA_MH_LOAD(1, a_nxt1, k0 + 32);
-        DRLA_MH_LOAD(2, a_nxt2, k0 + 32); DRLA_MH_LOAD(3, a_nxt3, k0 + 32);
+enum { MH_NONE = 0, MH_BIAS = 1, MH_MASK = 2 };
+
+// this wave's 64 output columns start here (wave-uniform, and known to be)
+__device__ __forceinline__ int mh_out0() {
+  return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 64;
+}
+
+template <int KCH>
+__device__ __forceinline__ void mh_load(MhFrags<KCH>& f,
+                                        const bf16raw* __restrict__ M,
+                                        int nout) {
+  const int lane = threadIdx.x % 64;
+  const int out0 = mh_out0();
+  const int kf = (lane >> 4) * 8;
+  if (out0 < nout) {
+#pragma unroll
+    for (int kc = 0; kc < KCH; ++kc) {
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const int orow = min(out0 + ni * 16 + (lane & 15), nout - 1);
+        f.a[kc][ni] = *reinterpret_cast<const bf16x8*>(
+            M + (long long)orow * (KCH * 32) + kc * 32 + kf);
       }
-      const bf16x8 b_frag =
-          *reinterpret_cast<const bf16x8*>(&act_in[lane & 15][k0 + kf]);
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur0, b_frag,
-                                                       acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur1, b_frag,
-                                                       acc[1], 0, 0, 0);
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur2, b_frag,
-                                                       acc[2], 0, 0, 0);
-      acc[3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur3, b_frag,
-                                                       acc[3], 0, 0, 0);
-      a_cur0 = a_nxt0; a_cur1 = a_nxt1; a_cur2 = a_nxt2; a_cur3 = a_nxt3;
     }
-#undef DRLA_MH_LOAD
   }
+}
+
+__device__ __forceinline__ void mh_load_bias(MhSide& s,
+                                             const bf16raw* __restrict__ bias,
+                                             int nout) {
+  const int lane = threadIdx.x % 64;
+  const int out0 = mh_out0();
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int oc = out0 + ni * 16 + (lane >> 4) * 4 + r;
+      s.v[ni][r] = bias[min(oc, nout - 1)];
+    }
+  }
+}
+
+// mask_stash [N, MH_HID]; the masked passes all have nout == MH_HID
+__device__ __forceinline__ void mh_load_mask(
+    MhSide& s, const bf16raw* __restrict__ mask_stash, int row0, int N) {
+  const int lane = threadIdx.x % 64;
+  const int out0 = mh_out0();
+  const long long grow = min(row0 + (lane & 15), N - 1);
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int oc = out0 + ni * 16 + (lane >> 4) * 4 + r;
+      s.v[ni][r] = mask_stash[grow * MH_HID + oc];
+    }
+  }
+}
+
+template <int KCH>
+__device__ __forceinline__ void mh_mma(f32x4 (&acc)[4],
+                                       const MhFrags<KCH>& f,
+                                       const bf16raw (*act_in)[MH_LD],
+                                       int nout) {
+  const int lane = threadIdx.x % 64;
+  const int out0 = mh_out0();
+  const int kf = (lane >> 4) * 8;
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
+  if (out0 < nout) {
+#pragma unroll
+    for (int kc = 0; kc < KCH; ++kc) {
+      const bf16x8 b_frag = *reinterpret_cast<const bf16x8*>(
+          &act_in[lane & 15][kc * 32 + kf]);
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const int orow = out0 + ni * 16 + (lane & 15);
+        const bf16x8 a_frag =
+            (nout == MH_HID || orow < nout) ? f.a[kc][ni] : zero8;
+        acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a_frag, b_frag, acc[ni], 0, 0, 0);
+      }
+    }
+  }
+}
+
+template <bool RELU, int SIDE>
+__device__ __forceinline__ void mh_epilogue(
+    const f32x4 (&acc)[4], bf16raw (*act_out)[MH_LD],
+    const MhSide& side,                      // bias or mask values, per SIDE
+    bf16raw* __restrict__ dz_global,         // [N,256]
+    float* __restrict__ colsum,              // [256]
+    bf16raw* __restrict__ stash,             // [N,nout] or null
+    float* __restrict__ dh_global,           // [N,256] or null
+    int row0, int N, int nout) {
+  const int lane = threadIdx.x % 64;
+  const int out0 = mh_out0();
+  const bool live = out0 < nout;
   __syncthreads();
   // epilogue: D[out][row] un-transpose -> act_out[row][out] (+stash/dz/dh);
   // per (ni, r) the lane touches ONE output column across its two rows, so
   // bias partials need one LDS atomic per (ni, r).
   if (live) {
+#pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
+#pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int oc = out0 + ni * 16 + (lane >> 4) * 4 + r;
         const int lrow = lane & 15;
         const int grow = row0 + lrow;
         float v = acc[ni][r];
-        if (bias) v += (oc < nout) ? mh_b2f(bias[oc]) : 0.0f;
+        if (SIDE == MH_BIAS) {
+          v += (oc < nout) ? mh_b2f(side.v[ni][r]) : 0.0f;
+        }
         if (RELU) v = fmaxf(v, 0.0f);
-        if (mask_stash) {
-          const float a = (grow < N)
-              ? mh_b2f(mask_stash[(long long)grow * MH_HID + oc]) : 0.0f;
+        if (SIDE == MH_MASK) {
+          const float a = (grow < N) ? mh_b2f(side.v[ni][r]) : 0.0f;
           v = (a > 0.0f) ? v : 0.0f;
         }
         if (dh_global) {
@@ -187,6 +262,27 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
   const bool policy = blockIdx.y == 0;
   const long long soff = (long long)N * MH_HID;
 
+  // the chain's operands; both chains run the same three passes
+  const bf16raw* W1 = policy ? W1p : W1v;
+  const bf16raw* W2 = policy ? W2p : W2v;
+  const bf16raw* W3 = policy ? W3p : W3v;
+  const bf16raw* b1 = policy ? b1p : b1v;
+  const bf16raw* b2 = policy ? b2p : b2v;
+  const bf16raw* b3 = policy ? b3p : b3v;
+  const int n3 = policy ? A : 1;
+  bf16raw* stash1 = stash + (policy ? 0 : 2 * soff);
+  bf16raw* stash2 = stash1 + soff;
+
+  // layers 1 and 2 entirely in flight before anything else happens (256
+  // VGPRs of fragments; one workgroup per CU, so they are there to use)
+  MhFrags<MH_HID / 32> fa, fb;
+  MhSide s1, s2, s3;
+  mh_load(fa, W1, MH_HID);
+  mh_load_bias(s1, b1, MH_HID);
+  mh_load(fb, W2, MH_HID);
+  mh_load_bias(s2, b2, MH_HID);
+  mh_load_bias(s3, b3, n3);
+
   if (wt_pack) {
     const int gt = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid;
     const int nt = gridDim.x * gridDim.y * 256;
@@ -232,10 +328,19 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
     const int r = tid >> 4;
     const int c0 = (tid & 15) * 16;
     const int grow = row0 + r;
+    // all 16 requested before the first is used (a load inside the store
+    // loop below waits for itself every time round)
+    // (and unconditionally, from a clamped row: a predicated load is a
+    // branch, and the wait comes back with it)
+    float hv[16];
+    const long long crow = min(grow, N - 1);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) hv[c] = h[crow * MH_HID + c0 + c];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) hv[c] = (grow < N) ? hv[c] : 0.0f;
+#pragma unroll
     for (int c = 0; c < 16; ++c) {
-      const float v = (grow < N) ? h[(long long)grow * MH_HID + c0 + c]
-                                 : 0.0f;
-      const bf16raw bv = drla_f32_to_bf16(v);
+      const bf16raw bv = drla_f32_to_bf16(hv[c]);
       hb[r][c0 + c] = bv;
       if (policy && grow < N) {
         stash[4 * soff + (long long)grow * MH_HID + c0 + c] = bv;
@@ -244,13 +349,19 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
   }
   __syncthreads();
 
+  f32x4 acc[4];
+  mh_mma(acc, fa, hb, MH_HID);
+  // layer 3 takes layer 1's registers as soon as its MFMAs have them
+  mh_load(fa, W3, n3);
+  mh_epilogue<true, MH_BIAS>(acc, acta, s1, nullptr, nullptr, stash1,
+                             nullptr, row0, N, MH_HID);
+  mh_mma(acc, fb, acta, MH_HID);
+  mh_epilogue<true, MH_BIAS>(acc, actb, s2, nullptr, nullptr, stash2,
+                             nullptr, row0, N, MH_HID);
+  mh_mma(acc, fa, actb, n3);
+  mh_epilogue<false, MH_BIAS>(acc, acta, s3, nullptr, nullptr, nullptr,
+                              nullptr, row0, N, n3);
   if (policy) {
-    mh_pass<true, false>(hb, acta, W1p, b1p, nullptr, nullptr, nullptr,
-                         stash, nullptr, row0, N, MH_HID, MH_HID);
-    mh_pass<true, false>(acta, actb, W2p, b2p, nullptr, nullptr, nullptr,
-                         stash + soff, nullptr, row0, N, MH_HID, MH_HID);
-    mh_pass<false, false>(actb, acta, W3p, b3p, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, row0, N, A, MH_HID);
     const int r = tid >> 3;
     const int c = tid & 7;
     if (r < MH_BM) {
@@ -261,18 +372,75 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
       }
     }
   } else {
-    mh_pass<true, false>(hb, acta, W1v, b1v, nullptr, nullptr, nullptr,
-                         stash + 2 * soff, nullptr, row0, N, MH_HID,
-                         MH_HID);
-    mh_pass<true, false>(acta, actb, W2v, b2v, nullptr, nullptr, nullptr,
-                         stash + 3 * soff, nullptr, row0, N, MH_HID,
-                         MH_HID);
-    mh_pass<false, false>(actb, acta, W3v, b3v, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, row0, N, 1, MH_HID);
     if (tid < MH_BM && row0 + tid < N) {
       value[row0 + tid] = mh_b2f(acta[tid][0]);
     }
   }
+}
+
+// The one-chunk-ahead form of the same pass in one function:
+// drla_mlp_heads_bwd keeps it, since requesting its chains' operands whole
+// buys that kernel nothing (KERNELS.md) and costs it a full register file.
+// Only the k-loop differs: the next chunk's fragments load while this
+// chunk's MFMAs run; the side values are requested behind the loop and the
+// epilogue is the shared one. M [nout][kdim] row-major, kdim a multiple of
+// 32; side_src: mask_stash [N,256] (MH_MASK), bias [nout] (MH_BIAS) or
+// unused (MH_NONE).
+template <bool RELU, int SIDE>
+__device__ void mh_pass(const bf16raw (*act_in)[MH_LD],
+                        bf16raw (*act_out)[MH_LD],
+                        const bf16raw* __restrict__ M,   // [nout][kdim]
+                        const bf16raw* __restrict__ side_src,
+                        bf16raw* __restrict__ dz_global,         // [N,256]
+                        float* __restrict__ colsum,              // [256]
+                        bf16raw* __restrict__ stash,     // [N,nout] or null
+                        float* __restrict__ dh_global,   // [N,256] or null
+                        int row0, int N, int nout, int kdim) {
+  const int lane = threadIdx.x % 64;
+  const int out0 = mh_out0();
+
+  f32x4 acc[4];
+  for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
+
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (out0 < nout) {
+    bf16x8 a_cur0, a_cur1, a_cur2, a_cur3;
+    const int kf = (lane >> 4) * 8;
+#define DRLA_MH_LOAD(ni, dst, k0)                                       \
+    {                                                                   \
+      const int orow = out0 + (ni) * 16 + (lane & 15);                  \
+      dst = (orow < nout)                                               \
+          ? *reinterpret_cast<const bf16x8*>(                           \
+                M + (long long)orow * kdim + (k0) + kf)                 \
+          : zero8;                                                      \
+    }
+    DRLA_MH_LOAD(0, a_cur0, 0); DRLA_MH_LOAD(1, a_cur1, 0);
+    DRLA_MH_LOAD(2, a_cur2, 0); DRLA_MH_LOAD(3, a_cur3, 0);
+    for (int k0 = 0; k0 < kdim; k0 += 32) {
+      bf16x8 a_nxt0, a_nxt1, a_nxt2, a_nxt3;
+      if (k0 + 32 < kdim) {
+        DRLA_MH_LOAD(0, a_nxt0, k0 + 32); DRLA_MH_LOAD(1, a_nxt1, k0 + 32);
+        DRLA_MH_LOAD(2, a_nxt2, k0 + 32); DRLA_MH_LOAD(3, a_nxt3, k0 + 32);
+      }
+      const bf16x8 b_frag =
+          *reinterpret_cast<const bf16x8*>(&act_in[lane & 15][k0 + kf]);
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur0, b_frag,
+                                                       acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur1, b_frag,
+                                                       acc[1], 0, 0, 0);
+      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur2, b_frag,
+                                                       acc[2], 0, 0, 0);
+      acc[3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur3, b_frag,
+                                                       acc[3], 0, 0, 0);
+      a_cur0 = a_nxt0; a_cur1 = a_nxt1; a_cur2 = a_nxt2; a_cur3 = a_nxt3;
+    }
+#undef DRLA_MH_LOAD
+  }
+  MhSide side;
+  if (SIDE == MH_MASK) mh_load_mask(side, side_src, row0, N);
+  if (SIDE == MH_BIAS) mh_load_bias(side, side_src, nout);
+  mh_epilogue<RELU, SIDE>(acc, act_out, side, dz_global, colsum, stash,
+                          dh_global, row0, N, nout);
 }
 
 // backward: takes PRE-TRANSPOSED weights (wrapper-built):
@@ -331,19 +499,19 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_bwd(
       atomicAdd(&db3p[tid], s);
     }
     __syncthreads();
-    mh_pass<false, false>(dza, dzb, wT3p, nullptr, a2p, dz2p, colsum,
-                          nullptr, nullptr, row0, N, MH_HID, 32);
+    mh_pass<false, MH_MASK>(dza, dzb, wT3p, a2p, dz2p, colsum, nullptr,
+                            nullptr, row0, N, MH_HID, 32);
     if (tid < MH_HID) {
       atomicAdd(&db2p[tid], colsum[tid]);
       colsum[tid] = 0.0f;
     }
     __syncthreads();
-    mh_pass<false, false>(dzb, dza, wT2p, nullptr, a1p, dz1p, colsum,
-                          nullptr, nullptr, row0, N, MH_HID, MH_HID);
+    mh_pass<false, MH_MASK>(dzb, dza, wT2p, a1p, dz1p, colsum, nullptr,
+                            nullptr, row0, N, MH_HID, MH_HID);
     if (tid < MH_HID) atomicAdd(&db1p[tid], colsum[tid]);
     __syncthreads();
-    mh_pass<false, false>(dza, dzb, wT1p, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, dh, row0, N, MH_HID, MH_HID);
+    mh_pass<false, MH_NONE>(dza, dzb, wT1p, nullptr, nullptr, nullptr,
+                            nullptr, dh, row0, N, MH_HID, MH_HID);
   } else {
     // ---- value chain ----
     // da2v[r][i] = dvalue[r] * W3v[i], masked by a2v
@@ -378,12 +546,12 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_bwd(
       atomicAdd(&db3v[0], s);
     }
     __syncthreads();
-    mh_pass<false, false>(dza, dzb, wT2v, nullptr, a1v, dz1v, colsum,
-                          nullptr, nullptr, row0, N, MH_HID, MH_HID);
+    mh_pass<false, MH_MASK>(dza, dzb, wT2v, a1v, dz1v, colsum, nullptr,
+                            nullptr, row0, N, MH_HID, MH_HID);
     if (tid < MH_HID) atomicAdd(&db1v[tid], colsum[tid]);
     __syncthreads();
-    mh_pass<false, true>(dzb, dza, wT1v, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, dh, row0, N, MH_HID, MH_HID);
+    mh_pass<false, MH_NONE>(dzb, dza, wT1v, nullptr, nullptr, nullptr,
+                            nullptr, dh, row0, N, MH_HID, MH_HID);
   }
 }
 
@@ -605,7 +773,11 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_fwd(
     bf16raw* __restrict__ w2t,            // [256,256] W2^T out (nullable)
     long long slab_stride,                // 0: out is [N,256] contiguous
     const float* __restrict__ h_src,      // [N,H] f32 (slab mode)
-    int H) {
+    int H,
+    const int* __restrict__ slot,         // drla_slot_base (nullable)
+    long long pa_dist, long long h_dist) {
+  pa = drla_slot_base(pa, slot, pa_dist);
+  h_src = drla_slot_base(h_src, slot, h_dist);
   // slab mode (slab_stride != 0): out points at the embedding columns of a
   // row-major [N, slab_stride] bf16 slab — the gate-GEMM input, assembled in
   // place. The block's 16 rows also get h (f32 -> bf16, the rounding of
@@ -615,6 +787,11 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_fwd(
   __shared__ bf16raw outimg[MH_BM][MH_LD];
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * MH_BM;
+  // W2 in flight under the table gather and the layer-1 epilogue below
+  MhFrags<MH_HID / 32> fw;
+  MhSide sb;
+  mh_load(fw, W2, MH_HID);
+  mh_load_bias(sb, b2, MH_HID);
   {
     const int r = tid >> 4;
     const int c0 = (tid & 15) * 16;
@@ -626,20 +803,29 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_fwd(
     // the backward scatter reads this copy, never the caller's buffer
     if (idx_stash && grow < N && (tid & 15) == 0) idx_stash[grow] = idx;
     const bf16raw* trow = table + idx * MH_HID + c0;
+    // requested together, ahead of the store loop
+    bf16raw tv[16], bv1[16];
+#pragma unroll
     for (int c = 0; c < 16; ++c) {
-      const float v =
-          fmaxf(mh_b2f(trow[c]) + mh_b2f(b1[c0 + c]), 0.0f);
+      tv[c] = trow[c];
+      bv1[c] = b1[c0 + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const float v = fmaxf(mh_b2f(tv[c]) + mh_b2f(bv1[c]), 0.0f);
       const bf16raw bv = drla_f32_to_bf16(v);
       a1img[r][c0 + c] = bv;
       if (grow < N) a1stash[(long long)grow * MH_HID + c0 + c] = bv;
     }
   }
   __syncthreads();
-  mh_pass<true, false>(a1img, outimg, W2, b2, nullptr, nullptr, nullptr,
-                       slab_stride ? nullptr : out, nullptr, row0, N, MH_HID,
-                       MH_HID);
+  f32x4 acc[4];
+  mh_mma(acc, fw, a1img, MH_HID);
+  mh_epilogue<true, MH_BIAS>(acc, outimg, sb, nullptr, nullptr,
+                             slab_stride ? nullptr : out, nullptr, row0, N,
+                             MH_HID);
   // the side outputs come AFTER the pass: nothing of theirs is live while
-  // the pass holds its weight fragments (VGPR budget / occupancy)
+  // the pass holds its weight fragments
   if (slab_stride != 0) {
     const int r = tid >> 4;
     const int c0 = (tid & 15) * 16;
@@ -712,6 +898,10 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
   __shared__ int srow[MH_BM];
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * MH_BM;
+  // W2^T in flight under the dz2 prologue below
+  MhFrags<MH_HID / 32> fw;
+  MhSide sm;
+  mh_load(fw, W2T, MH_HID);
   if (scat_idx && tid < MH_BM) {
     srow[tid] = (row0 + tid < N)
         ? drla_clamp_idx((int)scat_idx[row0 + tid], A) : -1;
@@ -723,14 +913,21 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
     const int c0 = (tid & 15) * 16;
     const int grow = row0 + r;
     float part[16];
+    // requested together, ahead of the store loop
+    // (from a clamped row: rows past N are zeroed below)
+    bf16raw ov[16], dv[16];
+    const long long crow = min(grow, N - 1);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      ov[c] = out[crow * out_stride + c0 + c];
+      dv[c] = dy[crow * dy_stride + c0 + c];
+    }
+#pragma unroll
     for (int c = 0; c < 16; ++c) {
       float v = 0.0f;
       if (grow < N) {
-        const float o =
-            mh_b2f(out[(long long)grow * out_stride + c0 + c]);
-        if (o > 0.0f) {
-          v = mh_b2f(dy[(long long)grow * dy_stride + c0 + c]);
-        }
+        const float o = mh_b2f(ov[c]);
+        if (o > 0.0f) v = mh_b2f(dv[c]);
       }
       const bf16raw bv = drla_f32_to_bf16(v);
       dz2img[r][c0 + c] = bv;
@@ -746,8 +943,12 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
   }
   __syncthreads();
   // dgrad through W2 with the ReLU1 mask and db1 column sums fused
-  mh_pass<false, false>(dz2img, da1img, W2T, nullptr, a1stash, da1,
-                        colsum, nullptr, nullptr, row0, N, MH_HID, MH_HID);
+  f32x4 acc[4];
+  mh_mma(acc, fw, dz2img, MH_HID);
+  // the mask values are requested here, behind the prologue's own loads
+  mh_load_mask(sm, a1stash, row0, N);
+  mh_epilogue<false, MH_MASK>(acc, da1img, sm, da1, colsum, nullptr,
+                              nullptr, row0, N, MH_HID);
   if (tid < MH_HID) atomicAdd(&bias_ws[tid], colsum[tid]);
   if (scat_idx) {
     // table scatter in the epilogue (was drla_embed_bwd_scatter re-reading

@@ -61,7 +61,14 @@ void drla_vtrace_loss_fwd(
     int B, int T, int A,
     float* __restrict__ partials,              // [>=B,4] (nullable)
     unsigned int* __restrict__ counter,        // [1] (with partials)
-    int* __restrict__ act_stash) {             // [B,T] (nullable)
+    int* __restrict__ act_stash,               // [B,T] (nullable)
+    const int* __restrict__ slot,              // drla_slot_base (nullable)
+    long long mu_dist, long long act_dist, long long rew_dist,
+    long long done_dist) {
+  mu = drla_slot_base(mu, slot, mu_dist);
+  actions = drla_slot_base(actions, slot, act_dist);
+  rewards = drla_slot_base(rewards, slot, rew_dist);
+  done = drla_slot_base(done, slot, done_dist);
   __shared__ float rho[VT_MAX_T];
   __shared__ float vsm[VT_MAX_T];
   __shared__ float rc[VT_MAX_T];

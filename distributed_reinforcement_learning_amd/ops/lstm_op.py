@@ -15,7 +15,7 @@ from typing import Tuple
 import torch
 
 from distributed_reinforcement_learning_amd import ops as _ops
-from distributed_reinforcement_learning_amd.ops import conv_op
+from distributed_reinforcement_learning_amd.ops import conv_op, input_slots
 
 # largest hidden size the LSTM sequence kernels take (ops/hip/drla_common.h
 # LSTM_SEQ_MAX_HIDDEN); the launchers refuse anything wider
@@ -33,8 +33,10 @@ class _FusedLstmTail(torch.autograd.Function):
         # backward's df = d_tc * c_prev reads the copy, not the caller's
         # buffer (it may be rewritten between forward and backward)
         stash_c = conv_op.STASH_INPUTS
+        slot, dist = input_slots.lookup(c_prev)
         res = ext.lstm_tail_fwd(gates.contiguous(), c_prev.contiguous(),
-                                forget_bias, stash_c=stash_c)
+                                forget_bias, stash_c=stash_c, slot=slot,
+                                slot_dist=[dist] if slot is not None else [])
         new_h, new_c, stash = res[:3]
         ctx.save_for_backward(stash, res[3] if stash_c else c_prev, new_c)
         ctx.bf16_gates = gates.dtype == torch.bfloat16

@@ -16,7 +16,7 @@ from typing import Tuple
 import torch
 
 from distributed_reinforcement_learning_amd import ops as _ops
-from distributed_reinforcement_learning_amd.ops import conv_op
+from distributed_reinforcement_learning_amd.ops import conv_op, input_slots
 
 _CLIP_MODE = {"abs_one": 0, "soft_asymmetric": 1, "none": 2}
 
@@ -34,11 +34,17 @@ class _FusedVtraceLoss(torch.autograd.Function):
         # between forward and backward (runtime/graphed.py)
         stash = conv_op.STASH_INPUTS
         actions = actions.contiguous()
+        # double-buffered static inputs: the kernel takes the set from the
+        # slot word (a field that is not registered has distance 0)
+        found = [input_slots.lookup(t)
+                 for t in (mu, actions, rewards, done)]
+        slot = next((s for s, _ in found if s is not None), None)
         res = ext.vtrace_loss_fwd(
             logits.contiguous(), value.contiguous(), mu.contiguous(),
             actions, rewards.contiguous(), done.contiguous(),
             gamma, clip_mode, c_bl, c_ent, nofill=True,
-            stash_actions=stash)
+            stash_actions=stash, slot=slot,
+            slot_dist=[d for _, d in found] if slot is not None else [])
         losses, p_stash, vs_stash, adv_stash = res[:4]
         ctx.save_for_backward(p_stash, vs_stash, adv_stash,
                               value.contiguous(),

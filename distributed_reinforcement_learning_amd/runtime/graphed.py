@@ -14,13 +14,18 @@ Two measured host-side traps shape this class (gpu_triage.py r03/r04):
     can produce data straight into ``self.pinned`` (the trajectory queue, the
     bench pool) skip it entirely.
 
-Step structure (three graphs + a copy stream):
-  host:     write decayed LR into a device buffer (never blocks)
+Step structure (three graphs + a copy stream). Every static input exists
+twice; a device slot word says which set a replay reads:
+  host:     one launch writes the decayed LR and the slot word (never blocks)
+  copy str: the NEXT batch's pinned -> static-input H2D into the OTHER set,
+            queued before graph 1 and ordered after the previous step's
+            graph 1 (that set's last reader), so the 19.4 MB upload has the
+            whole step to hide under. The four forward kernels that read
+            static inputs take the set from the slot word
+            (ops/input_slots.py, drla_slot_base)
   graph 1:  normalize frames, batched unroll (bf16), fused V-trace losses
-            (forward only)
-  copy str: the NEXT batch's pinned -> static-input H2D, ordered after
-            graph 1 via an event, so the ~18 MB upload hides behind the
-            backward. Every read of a static input happens INSIDE graph 1:
+            (forward only). Every read of a static input happens INSIDE
+            graph 1:
             each forward kernel that reads a backward-read input (conv-l1:
             state; embed MLP: previous_action; LSTM tail: initial_c;
             V-trace loss: action) stashes a copy in passing, no clone
@@ -47,7 +52,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from distributed_reinforcement_learning_amd.ops import conv_op
+from distributed_reinforcement_learning_amd import ops as _ops
+from distributed_reinforcement_learning_amd.ops import conv_op, input_slots
 from distributed_reinforcement_learning_amd.runtime._capture import (
     CapturedStep, OptimizerGraph, warmup_preserving_state,
 )
@@ -67,9 +73,11 @@ class GraphedImpalaStep(CapturedStep):
         dev = agent.device
 
         def z(shape, dtype):
-            return torch.zeros(shape, dtype=dtype, device=dev)
+            # two sets of every static input: the replay reads the set the
+            # device slot word names while the copy stream fills the other
+            return torch.zeros((2,) + tuple(shape), dtype=dtype, device=dev)
 
-        self.inputs: Dict[str, torch.Tensor] = {
+        self._pairs: Dict[str, torch.Tensor] = {
             "state": z((B, T, HH, WW, C), torch.uint8),
             "reward": z((B, T), torch.float32),
             # int32: the fused V-trace kernel consumes i32 and the ring
@@ -82,6 +90,13 @@ class GraphedImpalaStep(CapturedStep):
             "initial_h": z((B, T, H), torch.float32),
             "initial_c": z((B, T, H), torch.float32),
         }
+        self._sets = [{k: v[s] for k, v in self._pairs.items()}
+                      for s in (0, 1)]
+        # today's shapes and dtypes: views of set 0 (their storages cover
+        # both sets)
+        self.inputs: Dict[str, torch.Tensor] = self._sets[0]
+        self._slot_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._cur = 0  # the set the next replay reads
         self.pinned: Dict[str, torch.Tensor] = {
             k: torch.empty_like(v, device="cpu").pin_memory()
             for k, v in self.inputs.items()
@@ -97,14 +112,31 @@ class GraphedImpalaStep(CapturedStep):
         self._last_lr = 0.0
 
         opt = agent.optimizer
+        # the op wrappers hand the slot word and each field's set distance
+        # to the four forward kernels that read static inputs, for the
+        # warmup and the captures below (slot word 0 throughout)
+        input_slots.register(self._slot_word, self._pairs)
+        try:
+            self._warmup_and_capture(agent, opt, dev, warmup_iters)
+            # a field that reached something other than the four
+            # slot-aware kernels (a model on a torch fallback path) is read
+            # from set 0 whatever the word says: such a step keeps ONE set
+            # and the upload-after-forward ordering
+            self._double = not input_slots.unseen()
+        finally:
+            input_slots.clear()
+
+    def _warmup_and_capture(self, agent, opt, dev, warmup_iters):
         warmup_preserving_state(opt, self._fwd_bwd, warmup_iters, self.lr_buf)
 
         # ---- capture ------------------------------------------------------
-        # forward and backward are SEPARATE graphs so the next step's H2D
-        # upload (pinned -> static inputs, ~110 us) can overlap the
-        # backward on a copy stream; _fwd() confines every input read to
-        # graph 1 (in-kernel stashes of the backward-read fields), so the
-        # overlap cannot tear the backward's reads.
+        # forward and backward are SEPARATE graphs, and _fwd() confines
+        # every input read to graph 1 (in-kernel stashes of the
+        # backward-read fields): a set is free for the next upload as soon
+        # as the forward that read it is done. The upload is 19.4 MB in 8
+        # copies at B=32, T=20, measured 445 us first start to last end, the
+        # frames alone 329 us (profiles/impala_step_timeline_r04_parent.md);
+        # it no longer fits under the backward alone.
         self.g_fwd = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fwd):
             self._total, self.losses = self._fwd()
@@ -162,20 +194,26 @@ class GraphedImpalaStep(CapturedStep):
 
     def upload_inputs(self, src: Optional[Dict[str, torch.Tensor]] = None
                       ) -> None:
-        """Synchronous-path upload (priming / non-pipelined callers)."""
+        """Synchronous-path upload (priming / non-pipelined callers), into
+        the set the coming replay reads."""
         self._consumed.synchronize()
         src = src or self.pinned
-        for k, dst in self.inputs.items():
+        # a pipelined upload into this set may still be in flight
+        torch.cuda.current_stream().wait_event(self._uploaded)
+        for k, dst in self._sets[self._cur].items():
             dst.copy_(src[k], non_blocking=True)
         self._uploaded.record()
         self._primed = True
 
-    def _upload_overlapped(self, src: Dict[str, torch.Tensor]) -> None:
-        """Queue the NEXT step's H2D on the copy stream, ordered after this
-        step's forward (the only consumer of the static inputs)."""
+    def _upload_overlapped(self, src: Dict[str, torch.Tensor],
+                           into: int) -> None:
+        """Queue the NEXT step's H2D on the copy stream into set ``into``,
+        ordered after the PREVIOUS call's forward, the last reader of that
+        set: the upload runs under this call's forward, backward and
+        optimizer."""
         with torch.cuda.stream(self._copy_stream):
             self._copy_stream.wait_event(self._fwd_done)
-            for k, dst in self.inputs.items():
+            for k, dst in self._sets[into].items():
                 dst.copy_(src[k], non_blocking=True)
             self._uploaded.record(self._copy_stream)
 
@@ -196,8 +234,8 @@ class GraphedImpalaStep(CapturedStep):
         cadence.
 
         Pipelined upload (pinned paths only): the FIRST call uploads
-        synchronously; later calls replay on the inputs uploaded during the
-        PREVIOUS step's backward and queue this call's data on the copy
+        synchronously; later calls replay on the set uploaded during the
+        PREVIOUS call's step and queue this call's data into the other set
         stream — one-batch latency, which the asynchronous actor-learner
         loop does not notice (losses/scalars lag one batch). The numpy
         ``batch=`` path stays strictly synchronous."""
@@ -215,13 +253,26 @@ class GraphedImpalaStep(CapturedStep):
                 self.upload_inputs(src)
                 src = None
         main.wait_event(self._uploaded)
-        self._last_lr = self._opt.begin_step()
+        s = self._cur
+        # host side of the step (OptimizerGraph.begin_step's part, plus the
+        # slot word, in one launch): this replay reads set s
+        opt = agent.optimizer
+        self._last_lr = agent.lr_at(agent.global_step)
+        opt.step_count += 1
+        _ops.require_ext()._set_lr_slot(
+            self.lr_buf, self._slot_word,
+            float(opt.lr_t_for(self._last_lr, opt.step_count)), s)
+        if src is not None and self._double:
+            # this call's H2D goes into the other set, queued BEFORE the
+            # forward replay; the replay below consumes the PREVIOUS
+            # call's upload (one-batch pipeline)
+            self._upload_overlapped(src, 1 - s)
+            self._cur = 1 - s
         self.g_fwd.replay()
         self._fwd_done.record(main)
-        if src is not None:
-            # overlap this call's H2D with the backward; the replay above
-            # consumed the PREVIOUS call's upload (one-batch pipeline)
-            self._upload_overlapped(src)
+        if src is not None and not self._double:
+            # one set: its only reader is the forward just replayed
+            self._upload_overlapped(src, s)
         self.g_bwd.replay()
         self._opt.replay()
         self._consumed.record()
