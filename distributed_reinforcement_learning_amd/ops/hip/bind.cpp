@@ -1167,16 +1167,38 @@ std::vector<torch::Tensor> mlp_heads_wgrad(
 // train pair: Wh resident in LDS, H <= 123); every other size up to
 // LSTM_SEQ_MAX_HIDDEN runs the wide family, which streams Wh from global
 // memory.
-void check_lstm_seq_hidden(int H, const torch::Tensor& Wh) {
+struct LstmSeqGeom { bool wide, wh_in_lds; int block, lds_bytes; };
+
+LstmSeqGeom lstm_seq_geom(int H, const torch::Tensor& Wh, bool wide,
+                          bool wh_in_lds) {
   TORCH_CHECK(H >= 1 && H <= LSTM_SEQ_MAX_HIDDEN, "lstm hidden cap is ",
               LSTM_SEQ_MAX_HIDDEN, ", got H=", H);
   TORCH_CHECK(Wh.numel() == (int64_t)drla_lstm_seq_wh_elems(H),
               "Wh must be [H, 4H] for H=", H);
-}
-// the wide kernels read Wh as pairs of bf16
-void check_lstm_seq_wide_wh(const torch::Tensor& Wh) {
+  if (!wide) {
+    return {false, wh_in_lds, 4 * H, drla_lstm_seq_lds_bytes(H, wh_in_lds)};
+  }
+  // the wide kernels read Wh as pairs of bf16
   TORCH_CHECK(reinterpret_cast<uintptr_t>(Wh.data_ptr()) % 4 == 0,
               "lstm wide kernels need a 4-byte aligned Wh");
+  return {true, false, LSTM_SEQ_WIDE_BLOCK, drla_lstm_seq_wide_lds_bytes(H)};
+}
+// no-grad: wide when there are more gates than one block has threads; a Wh
+// too large for LDS is read from global memory instead
+LstmSeqGeom lstm_seq_geom_nograd(int H, const torch::Tensor& Wh) {
+  return lstm_seq_geom(H, Wh, 4 * H > LSTM_SEQ_MAX_GATES,
+                       drla_lstm_seq_wh_fits_lds(H));
+}
+LstmSeqGeom lstm_seq_geom_train(int H, const torch::Tensor& Wh) {
+  return lstm_seq_geom(H, Wh, !drla_lstm_seq_train_in_lds(H), true);
+}
+
+// the outputs both forward launchers have
+struct LstmSeqOut { torch::Tensor h_out, h_fin, c_fin; };
+LstmSeqOut lstm_seq_alloc_out(const torch::Tensor& h0, int B, int L, int H) {
+  auto fopt = h0.options().dtype(torch::kFloat);
+  return {torch::empty({B, L, H}, fopt), torch::empty({B, H}, fopt),
+          torch::empty({B, H}, fopt)};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_seq_fwd(
@@ -1186,32 +1208,17 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lstm_seq_fwd(
   TORCH_CHECK(done.scalar_type() == torch::kBool, "done must be bool");
   const int B = xgates.size(0), L = xgates.size(1);
   const int H = xgates.size(2) / 4;
-  check_lstm_seq_hidden(H, Wh);
-  // a Wh too large for LDS is read from global memory instead
-  const bool wh_in_lds = drla_lstm_seq_wh_fits_lds(H);
+  const LstmSeqGeom geom = lstm_seq_geom_nograd(H, Wh);
   const DualPtr xg = dual_ptr(xgates);
-  auto fopt = h0.options().dtype(torch::kFloat);
-  auto h_out = torch::empty({B, L, H}, fopt);
-  auto h_fin = torch::empty({B, H}, fopt);
-  auto c_fin = torch::empty({B, H}, fopt);
-  if (4 * H > LSTM_SEQ_MAX_GATES) {  // more gates than one block has threads
-    check_lstm_seq_wide_wh(Wh);
-    hipLaunchKernelGGL(
-        drla_lstm_seq_wide_fwd, dim3(B), dim3(LSTM_SEQ_WIDE_BLOCK),
-        drla_lstm_seq_wide_lds_bytes(H), cur_stream(), xg.bf16, xg.f32,
-        BF16P(Wh), h0.data_ptr<float>(), c0.data_ptr<float>(), boolp(done),
-        h_out.data_ptr<float>(), h_fin.data_ptr<float>(),
-        c_fin.data_ptr<float>(), static_cast<float>(forget_bias), B, L, H);
-    return {h_out, h_fin, c_fin};
-  }
+  auto out = lstm_seq_alloc_out(h0, B, L, H);
   hipLaunchKernelGGL(
-      wh_in_lds ? drla_lstm_seq_fwd : drla_lstm_seq_fwd_gmem, dim3(B),
-      dim3(4 * H), drla_lstm_seq_lds_bytes(H, wh_in_lds), cur_stream(),
-      xg.bf16, xg.f32, BF16P(Wh), h0.data_ptr<float>(), c0.data_ptr<float>(),
-      boolp(done), h_out.data_ptr<float>(),
-      h_fin.data_ptr<float>(), c_fin.data_ptr<float>(),
-      static_cast<float>(forget_bias), B, L, H);
-  return {h_out, h_fin, c_fin};
+      geom.wide ? drla_lstm_seq_wide_fwd
+                : geom.wh_in_lds ? drla_lstm_seq_fwd : drla_lstm_seq_fwd_gmem,
+      dim3(B), dim3(geom.block), geom.lds_bytes, cur_stream(), xg.bf16,
+      xg.f32, BF16P(Wh), h0.data_ptr<float>(), c0.data_ptr<float>(),
+      boolp(done), out.h_out.data_ptr<float>(), out.h_fin.data_ptr<float>(),
+      out.c_fin.data_ptr<float>(), static_cast<float>(forget_bias), B, L, H);
+  return {out.h_out, out.h_fin, out.c_fin};
 }
 
 void grad_gather(torch::Tensor srcs, torch::Tensor offs,
@@ -1244,28 +1251,20 @@ std::vector<torch::Tensor> lstm_seq_train_fwd(
     torch::Tensor done, double forget_bias) {
   check_all_gpu_contig("lstm_seq_train input", xg, Wh, h0, c0, done);
   const int B = xg.size(0), L = xg.size(1), H = xg.size(2) / 4;
-  check_lstm_seq_hidden(H, Wh);
-  const bool wide = !drla_lstm_seq_train_in_lds(H);
-  if (wide) check_lstm_seq_wide_wh(Wh);
-  auto fopt = h0.options().dtype(torch::kFloat);
-  auto h_out = torch::empty({B, L, H}, fopt);
-  auto h_fin = torch::empty({B, H}, fopt);
-  auto c_fin = torch::empty({B, H}, fopt);
-  auto acts = torch::empty({B, L, 4 * H}, fopt);
-  auto c_prev = torch::empty({B, L, H}, fopt);
+  const LstmSeqGeom geom = lstm_seq_geom_train(H, Wh);
+  auto out = lstm_seq_alloc_out(h0, B, L, H);
+  auto acts = torch::empty({B, L, 4 * H}, out.h_out.options());
+  auto c_prev = torch::empty({B, L, H}, out.h_out.options());
   auto h_prev = torch::empty({B, L, H}, xg.options());
-  hipLaunchKernelGGL(wide ? drla_lstm_seq_wide_train_fwd
-                          : drla_lstm_seq_train_fwd,
-                     dim3(B), dim3(wide ? LSTM_SEQ_WIDE_BLOCK : 4 * H),
-                     wide ? drla_lstm_seq_wide_lds_bytes(H)
-                          : drla_lstm_seq_lds_bytes(H),
-                     cur_stream(), BF16P(xg), BF16P(Wh),
-                     h0.data_ptr<float>(), c0.data_ptr<float>(), boolp(done),
-                     h_out.data_ptr<float>(), h_fin.data_ptr<float>(),
-                     c_fin.data_ptr<float>(), acts.data_ptr<float>(),
-                     c_prev.data_ptr<float>(), BF16PM(h_prev),
-                     static_cast<float>(forget_bias), B, L, H);
-  return {h_out, h_fin, c_fin, acts, c_prev, h_prev};
+  hipLaunchKernelGGL(
+      geom.wide ? drla_lstm_seq_wide_train_fwd : drla_lstm_seq_train_fwd,
+      dim3(B), dim3(geom.block), geom.lds_bytes, cur_stream(), BF16P(xg),
+      BF16P(Wh), h0.data_ptr<float>(), c0.data_ptr<float>(), boolp(done),
+      out.h_out.data_ptr<float>(), out.h_fin.data_ptr<float>(),
+      out.c_fin.data_ptr<float>(), acts.data_ptr<float>(),
+      c_prev.data_ptr<float>(), BF16PM(h_prev),
+      static_cast<float>(forget_bias), B, L, H);
+  return {out.h_out, out.h_fin, out.c_fin, acts, c_prev, h_prev};
 }
 
 std::vector<torch::Tensor> lstm_seq_train_bwd(
@@ -1275,19 +1274,16 @@ std::vector<torch::Tensor> lstm_seq_train_bwd(
   check_all_gpu_contig("lstm_seq_train bwd input", dh_out, acts, c_prev, Wh,
                        done);
   const int B = acts.size(0), L = acts.size(1), H = acts.size(2) / 4;
-  check_lstm_seq_hidden(H, Wh);
-  const bool wide = !drla_lstm_seq_train_in_lds(H);
-  if (wide) check_lstm_seq_wide_wh(Wh);
+  const LstmSeqGeom geom = lstm_seq_geom_train(H, Wh);
   auto fopt = dh_out.options().dtype(torch::kFloat);
   auto dxg = torch::empty({B, L, 4 * H},
                           dh_out.options().dtype(torch::kBFloat16));
   auto dh0 = torch::empty({B, H}, fopt);
   auto dc0 = torch::empty({B, H}, fopt);
   hipLaunchKernelGGL(
-      wide ? drla_lstm_seq_wide_train_bwd : drla_lstm_seq_train_bwd, dim3(B),
-      dim3(wide ? LSTM_SEQ_WIDE_BLOCK : 4 * H),
-      wide ? drla_lstm_seq_wide_lds_bytes(H) : drla_lstm_seq_lds_bytes(H),
-      cur_stream(), dh_out.data_ptr<float>(),
+      geom.wide ? drla_lstm_seq_wide_train_bwd : drla_lstm_seq_train_bwd,
+      dim3(B), dim3(geom.block), geom.lds_bytes, cur_stream(),
+      dh_out.data_ptr<float>(),
       dh_fin.has_value() ? dh_fin->data_ptr<float>() : nullptr,
       dc_fin.has_value() ? dc_fin->data_ptr<float>() : nullptr,
       acts.data_ptr<float>(), c_prev.data_ptr<float>(), BF16P(Wh),

@@ -28,11 +28,6 @@
 #define CONV_KERNEL \
   extern "C" __global__ __launch_bounds__(DRLA_CONV_BLOCK) void
 
-__device__ __forceinline__ float cv_bf2f(bf16raw u) {
-  unsigned int x = ((unsigned int)u) << 16;
-  return __uint_as_float(x);
-}
-
 // ---------------------------------------------------------------------------
 // layout probe: D = A @ B for one 16x16x32 tile, used by tests to pin the
 // fragment maps empirically (guide §3: check with ASYMMETRIC operands).
@@ -86,7 +81,7 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
   const int lane = tid % 64;
   const int row0 = blockIdx.x * BM;
 
-  if (tid < CO) BiasBuf[tid] = cv_bf2f(bias[tid]);
+  if (tid < CO) BiasBuf[tid] = drla_bf16_to_f32(bias[tid]);
 
   f32x4 acc[2][NFRAG];
   for (int mi = 0; mi < 2; ++mi)
@@ -348,12 +343,12 @@ extern "C" __global__ void drla_relu_mask_bwd(
     const bf16raw d0 = (bf16raw)((dw) & 0xFFFF);                      \
     const bf16raw d1 = (bf16raw)((dw) >> 16);                         \
     const bf16raw m0 =                                                \
-        (cv_bf2f((bf16raw)((yw) & 0xFFFF)) > 0.0f) ? d0 : (bf16raw)0; \
+        (drla_bf16_to_f32((bf16raw)((yw) & 0xFFFF)) > 0.0f) ? d0 : (bf16raw)0; \
     const bf16raw m1 =                                                \
-        (cv_bf2f((bf16raw)((yw) >> 16)) > 0.0f) ? d1 : (bf16raw)0;    \
+        (drla_bf16_to_f32((bf16raw)((yw) >> 16)) > 0.0f) ? d1 : (bf16raw)0;    \
     (ow) = ((unsigned int)m1 << 16) | m0;                             \
-    (a0) += cv_bf2f(m0);                                              \
-    (a1) += cv_bf2f(m1);                                              \
+    (a0) += drla_bf16_to_f32(m0);                                              \
+    (a1) += drla_bf16_to_f32(m1);                                              \
   }
   const long long row8 = row_elems / 8;
   const bool strided = (n_stride != row_elems);

@@ -134,6 +134,12 @@ __device__ __forceinline__ float drla_sigmoid(float x) {
   return 1.0f / (1.0f + __expf(-x));
 }
 
+// bf16 raw bits -> f32 (exact: the bits become the high half)
+__device__ __forceinline__ float drla_bf16_to_f32(bf16raw u) {
+  unsigned int x = ((unsigned int)u) << 16;
+  return __uint_as_float(x);
+}
+
 // round-to-nearest-even f32 -> bf16 raw bits. gfx950 has a hardware
 // packed convert (v_cvt_pk_bf16_f32, 1 VALU op); the bit-math expansion
 // costs ~6 ops per value and showed up in the staging-heavy kernels

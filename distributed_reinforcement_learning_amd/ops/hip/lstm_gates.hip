@@ -8,16 +8,71 @@
 //
 // Layout: gates [N, 4H] row-major, states [N, H]. One lane per (n, h) cell;
 // fully coalesced; stash holds the post-activation gates for backward.
+//
+// The cell math is written once, in lstm_cell_fwd / lstm_cell_bwd; the per
+// step work of the sequence kernels around it (stashes, done mask) once, in
+// lstm_seq_step_fwd / lstm_seq_step_bwd. Every kernel below calls these.
+// The expressions contract into FMAs at the compiler's choice: keep their
+// operand order and where their operands are loaded (KERNELS.md, K3).
 
 #include "drla_kernels.h"
 
-__device__ __forceinline__ float lstm_b2f(bf16raw u) {
-  unsigned int x = ((unsigned int)u) << 16;
-  return __uint_as_float(x);
+__device__ __forceinline__ float lstm_ld(const float* p) { return *p; }
+__device__ __forceinline__ float lstm_ld(const bf16raw* p) {
+  return drla_bf16_to_f32(*p);
+}
+__device__ __forceinline__ void lstm_st(float* p, float v) { *p = v; }
+__device__ __forceinline__ void lstm_st(bf16raw* p, float v) {
+  *p = drla_f32_to_bf16(v);
 }
 
-extern "C" __global__ void drla_lstm_tail_fwd(
-    const float* __restrict__ gates, const float* __restrict__ c_prev,
+struct LstmCell { float i_s, g_t, f_s, o_s, c_prev, c_new, h_new; };
+
+// gates[k * H], k = 0..3: the pre-activations in gate order [i, g, f, o]
+// -> activated gates, c', h'. Every value is loaded where it is first used:
+// with both products of c' open to contraction, the compiler's pick follows
+// the order of definitions.
+template <typename GT>
+__device__ __forceinline__ LstmCell lstm_cell_fwd(
+    const GT* gates, int H, float forget_bias, const float* c_prev) {
+  LstmCell r;
+  r.i_s = drla_sigmoid(lstm_ld(gates));
+  r.g_t = tanhf(lstm_ld(gates + H));
+  r.f_s = drla_sigmoid(lstm_ld(gates + 2 * H) + forget_bias);
+  r.o_s = drla_sigmoid(lstm_ld(gates + 3 * H));
+  r.c_prev = *c_prev;
+  r.c_new = r.f_s * r.c_prev + r.i_s * r.g_t;
+  r.h_new = r.o_s * tanhf(r.c_new);
+  return r;
+}
+
+struct LstmCellGrad { float di, dg, df, do_, dc_prev; };  // pre-act grads
+
+// tc = tanh(c'), from wherever the caller has c' (the tail kernels read
+// new_c, the sequence kernels recompute it from their stash)
+__device__ __forceinline__ LstmCellGrad lstm_cell_bwd(
+    float i_s, float g_t, float f_s, float o_s, float c_prev, float tc,
+    float dh, float dc) {
+  const float d_tc = dh * o_s * (1.0f - tc * tc) + dc;
+  const float di = d_tc * g_t;
+  const float dg = d_tc * i_s;
+  const float df = d_tc * c_prev;
+  const float do_ = dh * tc;
+  LstmCellGrad r;
+  r.di = di * i_s * (1.0f - i_s);
+  r.dg = dg * (1.0f - g_t * g_t);
+  r.df = df * f_s * (1.0f - f_s);
+  r.do_ = do_ * o_s * (1.0f - o_s);
+  r.dc_prev = d_tc * f_s;
+  return r;
+}
+
+// GT = float, or bf16raw: the gate GEMM (addmm) emits bf16; reading it
+// directly (and emitting bf16 grad_gates) removes the [N,4H] f32 cast
+// kernel on each side of the tail (~2 x 4.7 us/step).
+template <typename GT>
+__device__ __forceinline__ void lstm_tail_fwd_impl(
+    const GT* __restrict__ gates, const float* __restrict__ c_prev,
     float* __restrict__ new_h, float* __restrict__ new_c,
     float* __restrict__ stash,  // [N,4H] activated gates (i,g,f,o)
     float forget_bias, long long N, int H,
@@ -31,128 +86,146 @@ extern "C" __global__ void drla_lstm_tail_fwd(
     const long long n = idx / H;
     const int h = idx - n * H;
     const long long g0 = n * 4LL * H + h;
-    const float i_s = drla_sigmoid(gates[g0]);
-    const float g_t = tanhf(gates[g0 + H]);
-    const float f_s = drla_sigmoid(gates[g0 + 2 * H] + forget_bias);
-    const float o_s = drla_sigmoid(gates[g0 + 3 * H]);
-    const float c_in = c_prev[idx];
-    if (c_stash) c_stash[idx] = c_in;
-    const float c_new = f_s * c_in + i_s * g_t;
-    new_c[idx] = c_new;
-    new_h[idx] = o_s * tanhf(c_new);
-    stash[g0] = i_s;
-    stash[g0 + H] = g_t;
-    stash[g0 + 2 * H] = f_s;
-    stash[g0 + 3 * H] = o_s;
+    const LstmCell r = lstm_cell_fwd(gates + g0, H, forget_bias,
+                                     c_prev + idx);
+    if (c_stash) c_stash[idx] = r.c_prev;
+    new_c[idx] = r.c_new;
+    new_h[idx] = r.h_new;
+    stash[g0] = r.i_s;
+    stash[g0 + H] = r.g_t;
+    stash[g0 + 2 * H] = r.f_s;
+    stash[g0 + 3 * H] = r.o_s;
   }
 }
 
 // grad_c may be null (the cell's new_c is unused downstream — IMPALA's
 // batched unroll consumes only new_h — so autograd has no c-grad; the
 // null saves a [N,H] zero-fill per step)
+template <typename GT>
+__device__ __forceinline__ void lstm_tail_bwd_impl(
+    const float* __restrict__ grad_h, const float* __restrict__ grad_c,
+    const float* __restrict__ stash, const float* __restrict__ c_prev,
+    const float* __restrict__ new_c, GT* __restrict__ grad_gates,
+    float* __restrict__ grad_c_prev, long long N, int H,
+    long long gh_stride) {
+  long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  const long long total = N * H;
+  const long long stride = gridDim.x * (long long)blockDim.x;
+  for (; idx < total; idx += stride) {
+    const long long n = idx / H;
+    const int h = idx - n * H;
+    const long long g0 = n * 4LL * H + h;
+    const LstmCellGrad r = lstm_cell_bwd(
+        stash[g0], stash[g0 + H], stash[g0 + 2 * H], stash[g0 + 3 * H],
+        c_prev[idx], tanhf(new_c[idx]), grad_h[n * gh_stride + h],
+        grad_c ? grad_c[idx] : 0.0f);
+    grad_c_prev[idx] = r.dc_prev;
+    lstm_st(grad_gates + g0, r.di);
+    lstm_st(grad_gates + g0 + H, r.dg);
+    lstm_st(grad_gates + g0 + 2 * H, r.df);
+    lstm_st(grad_gates + g0 + 3 * H, r.do_);
+  }
+}
+
+extern "C" __global__ void drla_lstm_tail_fwd(
+    const float* __restrict__ gates, const float* __restrict__ c_prev,
+    float* __restrict__ new_h, float* __restrict__ new_c,
+    float* __restrict__ stash, float forget_bias, long long N, int H,
+    float* __restrict__ c_stash, const int* __restrict__ slot,
+    long long c_dist) {
+  lstm_tail_fwd_impl(gates, c_prev, new_h, new_c, stash, forget_bias, N, H,
+                     c_stash, slot, c_dist);
+}
+
+extern "C" __global__ void drla_lstm_tail_fwd_bf16(
+    const bf16raw* __restrict__ gates, const float* __restrict__ c_prev,
+    float* __restrict__ new_h, float* __restrict__ new_c,
+    float* __restrict__ stash, float forget_bias, long long N, int H,
+    float* __restrict__ c_stash, const int* __restrict__ slot,
+    long long c_dist) {
+  lstm_tail_fwd_impl(gates, c_prev, new_h, new_c, stash, forget_bias, N, H,
+                     c_stash, slot, c_dist);
+}
+
 extern "C" __global__ void drla_lstm_tail_bwd(
     const float* __restrict__ grad_h, const float* __restrict__ grad_c,
     const float* __restrict__ stash, const float* __restrict__ c_prev,
     const float* __restrict__ new_c, float* __restrict__ grad_gates,
     float* __restrict__ grad_c_prev, long long N, int H,
     long long gh_stride) {
-  long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  const long long total = N * H;
-  const long long stride = gridDim.x * (long long)blockDim.x;
-  for (; idx < total; idx += stride) {
-    const long long n = idx / H;
-    const int h = idx - n * H;
-    const long long g0 = n * 4LL * H + h;
-    const float i_s = stash[g0];
-    const float g_t = stash[g0 + H];
-    const float f_s = stash[g0 + 2 * H];
-    const float o_s = stash[g0 + 3 * H];
-    const float tc = tanhf(new_c[idx]);
-    const float dh = grad_h[n * gh_stride + h];
-    const float gc = grad_c ? grad_c[idx] : 0.0f;
-    const float d_tc = dh * o_s * (1.0f - tc * tc) + gc;
-    grad_c_prev[idx] = d_tc * f_s;
-    const float di = d_tc * g_t;
-    const float dg = d_tc * i_s;
-    const float df = d_tc * c_prev[idx];
-    const float do_ = dh * tc;
-    grad_gates[g0] = di * i_s * (1.0f - i_s);
-    grad_gates[g0 + H] = dg * (1.0f - g_t * g_t);
-    grad_gates[g0 + 2 * H] = df * f_s * (1.0f - f_s);
-    grad_gates[g0 + 3 * H] = do_ * o_s * (1.0f - o_s);
-  }
-}
-
-// bf16-gates variants: the gate GEMM (addmm) emits bf16; reading it
-// directly (and emitting bf16 grad_gates) removes the [N,4H] f32 cast
-// kernel on each side of the tail (~2 x 4.7 us/step).
-extern "C" __global__ void drla_lstm_tail_fwd_bf16(
-    const unsigned short* __restrict__ gates,
-    const float* __restrict__ c_prev, float* __restrict__ new_h,
-    float* __restrict__ new_c, float* __restrict__ stash, float forget_bias,
-    long long N, int H,
-    float* __restrict__ c_stash,    // [N,H] copy of c_prev (nullable)
-    const int* __restrict__ slot, long long c_dist) {  // drla_slot_base
-  c_prev = drla_slot_base(c_prev, slot, c_dist);
-  long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  const long long total = N * H;
-  const long long stride = gridDim.x * (long long)blockDim.x;
-  for (; idx < total; idx += stride) {
-    const long long n = idx / H;
-    const int h = idx - n * H;
-    const long long g0 = n * 4LL * H + h;
-    const float i_s = drla_sigmoid(lstm_b2f(gates[g0]));
-    const float g_t = tanhf(lstm_b2f(gates[g0 + H]));
-    const float f_s = drla_sigmoid(lstm_b2f(gates[g0 + 2 * H])
-                                   + forget_bias);
-    const float o_s = drla_sigmoid(lstm_b2f(gates[g0 + 3 * H]));
-    const float c_in = c_prev[idx];
-    if (c_stash) c_stash[idx] = c_in;
-    const float c_new = f_s * c_in + i_s * g_t;
-    new_c[idx] = c_new;
-    new_h[idx] = o_s * tanhf(c_new);
-    stash[g0] = i_s;
-    stash[g0 + H] = g_t;
-    stash[g0 + 2 * H] = f_s;
-    stash[g0 + 3 * H] = o_s;
-  }
+  lstm_tail_bwd_impl(grad_h, grad_c, stash, c_prev, new_c, grad_gates,
+                     grad_c_prev, N, H, gh_stride);
 }
 
 extern "C" __global__ void drla_lstm_tail_bwd_bf16(
     const float* __restrict__ grad_h, const float* __restrict__ grad_c,
     const float* __restrict__ stash, const float* __restrict__ c_prev,
-    const float* __restrict__ new_c, unsigned short* __restrict__ grad_gates,
+    const float* __restrict__ new_c, bf16raw* __restrict__ grad_gates,
     float* __restrict__ grad_c_prev, long long N, int H,
     long long gh_stride) {
-  long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  const long long total = N * H;
-  const long long stride = gridDim.x * (long long)blockDim.x;
-  for (; idx < total; idx += stride) {
-    const long long n = idx / H;
-    const int h = idx - n * H;
-    const long long g0 = n * 4LL * H + h;
-    const float i_s = stash[g0];
-    const float g_t = stash[g0 + H];
-    const float f_s = stash[g0 + 2 * H];
-    const float o_s = stash[g0 + 3 * H];
-    const float tc = tanhf(new_c[idx]);
-    const float dh = grad_h[n * gh_stride + h];
-    const float gc = grad_c ? grad_c[idx] : 0.0f;
-    const float d_tc = dh * o_s * (1.0f - tc * tc) + gc;
-    grad_c_prev[idx] = d_tc * f_s;
-    const float di = d_tc * g_t;
-    const float dg = d_tc * i_s;
-    const float df = d_tc * c_prev[idx];
-    const float do_ = dh * tc;
-    grad_gates[g0] = drla_f32_to_bf16(di * i_s * (1.0f - i_s));
-    grad_gates[g0 + H] = drla_f32_to_bf16(dg * (1.0f - g_t * g_t));
-    grad_gates[g0 + 2 * H] = drla_f32_to_bf16(df * f_s * (1.0f - f_s));
-    grad_gates[g0 + 3 * H] = drla_f32_to_bf16(do_ * o_s * (1.0f - o_s));
+  lstm_tail_bwd_impl(grad_h, grad_c, stash, c_prev, new_c, grad_gates,
+                     grad_c_prev, N, H, gh_stride);
+}
+
+// ---------------------------------------------------------------------------
+// Sequence kernels: the per-step work of one hidden unit j of batch row
+// `row / L`, shared by the narrow and the wide family. gates / dg4 are the
+// [4H] LDS gate buffers, hbuf / cbuf / dhc / dcc the [H] LDS carries.
+// ---------------------------------------------------------------------------
+
+// STASH (train forward): activated gates [B,L,4H] f32, c_prev [B,L,H] f32
+// and h_prev [B,L,H] bf16 (consumed by the dWh GEMM).
+template <bool STASH>
+__device__ __forceinline__ void lstm_seq_step_fwd(
+    const float* gates, float* hbuf, float* cbuf, float* __restrict__ h_out,
+    float* __restrict__ acts, float* __restrict__ c_prev_st,
+    bf16raw* __restrict__ h_prev_st, float forget_bias, float keep,
+    long long row, int j, int H) {
+  const long long sb = row * H + j;
+  const LstmCell r = lstm_cell_fwd(gates + j, H, forget_bias, cbuf + j);
+  if (STASH) {
+    const long long ab = row * 4 * H;
+    h_prev_st[sb] = drla_f32_to_bf16(hbuf[j]);
+    c_prev_st[sb] = r.c_prev;
+    acts[ab + j] = r.i_s;
+    acts[ab + H + j] = r.g_t;
+    acts[ab + 2 * H + j] = r.f_s;
+    acts[ab + 3 * H + j] = r.o_s;
   }
+  h_out[sb] = r.h_new;
+  // done-mask reset applies to the CARRY, not the emitted h
+  hbuf[j] = r.h_new * keep;
+  cbuf[j] = r.c_new * keep;
+}
+
+// Writes the four gate pre-activation grads to dg4 and the c carry to dcc;
+// the caller reduces dg4 against Wh into dhc.
+__device__ __forceinline__ void lstm_seq_step_bwd(
+    const float* __restrict__ dh_out, const float* __restrict__ acts,
+    const float* __restrict__ c_prev_st, float* dg4, const float* dhc,
+    float* dcc, float keep, long long row, int j, int H) {
+  const long long ab = row * 4 * H;
+  const long long sb = row * H + j;
+  const float i_s = acts[ab + j];
+  const float g_t = acts[ab + H + j];
+  const float f_s = acts[ab + 2 * H + j];
+  const float o_s = acts[ab + 3 * H + j];
+  const float cp = c_prev_st[sb];
+  const float c_new = f_s * cp + i_s * g_t;
+  // carry grads were stored PRE-mask; the forward applied keep_t to
+  // this step's outputs before carrying them into t+1
+  const float dh_new = dh_out[sb] + dhc[j] * keep;
+  const LstmCellGrad r = lstm_cell_bwd(i_s, g_t, f_s, o_s, cp, tanhf(c_new),
+                                       dh_new, dcc[j] * keep);
+  dg4[j] = r.di;
+  dg4[H + j] = r.dg;
+  dg4[2 * H + j] = r.df;
+  dg4[3 * H + j] = r.do_;
+  dcc[j] = r.dc_prev;  // pre-mask carry for t-1
 }
 
 // K3 sequence form (SURVEY §5.7a + BASELINE "burn_in hidden-state
-// recompute"): the WHOLE no-grad LSTM unroll in ONE kernel.
+// recompute"): the WHOLE LSTM unroll in ONE kernel.
 //
 // The x-projection (feat @ Wx + b) has no recurrence and runs as one
 // batched MFMA GEMM outside; only the tiny h @ Wh chain is sequential.
@@ -162,11 +235,14 @@ extern "C" __global__ void drla_lstm_tail_bwd_bf16(
 // consecutive Wh bytes (conflict-free). A hidden size whose Wh is larger
 // than LDS (H > 140, up to the 4H <= 1024 block cap) runs the same body
 // with Wh read from global memory, where its <= 512 KB stay L2-resident.
+// STASH is the forward WITH GRADIENTS of the R2D2 trained window; its
+// backward is drla_lstm_seq_train_bwd, and the x-projection GEMM, dWh GEMM
+// and bias reduce stay outside (MFMA-shaped, autograd/hipBLASLt).
 //
 // Replaces the reference's per-timestep replica chain
 // (r2d2_lstm.py:67-114): ~5 launches/step -> 1 launch per sequence.
 
-template <bool WH_IN_LDS>
+template <bool WH_IN_LDS, bool STASH>
 __device__ __forceinline__ void lstm_seq_fwd_impl(
     const bf16raw* __restrict__ xg16,  // [B,L,4H] (nullable)
     const float* __restrict__ xg32,      // [B,L,4H] (nullable)
@@ -177,7 +253,10 @@ __device__ __forceinline__ void lstm_seq_fwd_impl(
     float* __restrict__ h_out,           // [B,L,H]
     float* __restrict__ h_fin,           // [B,H]
     float* __restrict__ c_fin,           // [B,H]
-    float forget_bias, int B, int L, int H) {
+    float* __restrict__ acts,            // [B,L,4H]  (STASH only)
+    float* __restrict__ c_prev_st,       // [B,L,H]   (STASH only)
+    bf16raw* __restrict__ h_prev_st,   // [B,L,H]   (STASH only)
+    float forget_bias, int L, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16raw* wh_lds = reinterpret_cast<bf16raw*>(smem);    // [H*4H] or empty
   float* hbuf = reinterpret_cast<float*>(
@@ -199,29 +278,22 @@ __device__ __forceinline__ void lstm_seq_fwd_impl(
   __syncthreads();
 
   for (int t = 0; t < L; ++t) {
+    const long long row = (long long)b * L + t;
     // gates_h[j] = sum_k h[k] * Wh[k][j]
     float g = 0.0f;
     for (int k = 0; k < H; ++k) {
-      g = fmaf(hbuf[k], lstm_b2f(wh[k * G + j]), g);
+      g = fmaf(hbuf[k], drla_bf16_to_f32(wh[k * G + j]), g);
     }
-    const long long xbase = ((long long)b * L + t) * G + j;
-    g += xg16 ? lstm_b2f(xg16[xbase]) : xg32[xbase];
+    const long long xbase = row * G + j;
+    g += xg16 ? drla_bf16_to_f32(xg16[xbase]) : xg32[xbase];
     __shared__ float gates[LSTM_SEQ_MAX_GATES];
     static_assert(sizeof(gates) == LSTM_SEQ_STATIC_LDS_BYTES, "LDS budget");
     gates[j] = g;
     __syncthreads();
     if (j < H) {
-      const float i_s = drla_sigmoid(gates[j]);
-      const float g_t = tanhf(gates[H + j]);
-      const float f_s = drla_sigmoid(gates[2 * H + j] + forget_bias);
-      const float o_s = drla_sigmoid(gates[3 * H + j]);
-      const float c_new = f_s * cbuf[j] + i_s * g_t;
-      const float h_new = o_s * tanhf(c_new);
-      h_out[((long long)b * L + t) * H + j] = h_new;
-      // done-mask reset applies to the CARRY, not the emitted h
-      const float keep = done[(long long)b * L + t] ? 0.0f : 1.0f;
-      hbuf[j] = h_new * keep;
-      cbuf[j] = c_new * keep;
+      lstm_seq_step_fwd<STASH>(gates, hbuf, cbuf, h_out, acts, c_prev_st,
+                               h_prev_st, forget_bias,
+                               done[row] ? 0.0f : 1.0f, row, j, H);
     }
     __syncthreads();
   }
@@ -237,8 +309,9 @@ extern "C" __global__ void drla_lstm_seq_fwd(
     const float* __restrict__ c0, const unsigned char* __restrict__ done,
     float* __restrict__ h_out, float* __restrict__ h_fin,
     float* __restrict__ c_fin, float forget_bias, int B, int L, int H) {
-  lstm_seq_fwd_impl<true>(xg16, xg32, Wh, h0, c0, done, h_out, h_fin, c_fin,
-                          forget_bias, B, L, H);
+  lstm_seq_fwd_impl<true, false>(xg16, xg32, Wh, h0, c0, done, h_out, h_fin,
+                                 c_fin, nullptr, nullptr, nullptr,
+                                 forget_bias, L, H);
 }
 
 extern "C" __global__ void drla_lstm_seq_fwd_gmem(
@@ -247,85 +320,25 @@ extern "C" __global__ void drla_lstm_seq_fwd_gmem(
     const float* __restrict__ c0, const unsigned char* __restrict__ done,
     float* __restrict__ h_out, float* __restrict__ h_fin,
     float* __restrict__ c_fin, float forget_bias, int B, int L, int H) {
-  lstm_seq_fwd_impl<false>(xg16, xg32, Wh, h0, c0, done, h_out, h_fin, c_fin,
-                           forget_bias, B, L, H);
+  lstm_seq_fwd_impl<false, false>(xg16, xg32, Wh, h0, c0, done, h_out, h_fin,
+                                  c_fin, nullptr, nullptr, nullptr,
+                                  forget_bias, L, H);
 }
-
-// ---------------------------------------------------------------------------
-// K3 sequence form WITH GRADIENTS: the R2D2 trained window currently loops
-// L per-step cell calls (~6 launches each + backward). This pair runs the
-// whole recurrence as one kernel each way; the x-projection GEMM, dWh GEMM
-// and bias reduce stay outside (MFMA-shaped, autograd/hipBLASLt).
-// Stashes: activated gates [B,L,4H] f32, c_prev [B,L,H] f32 and h_prev
-// [B,L,H] bf16 (consumed by the dWh GEMM).
-// ---------------------------------------------------------------------------
 
 extern "C" __global__ void drla_lstm_seq_train_fwd(
-    const bf16raw* __restrict__ xg16,  // [B,L,4H]
-    const bf16raw* __restrict__ Wh,    // [H][4H]
-    const float* __restrict__ h0,        // [B,H]
-    const float* __restrict__ c0,        // [B,H]
-    const unsigned char* __restrict__ done,  // [B,L]
-    float* __restrict__ h_out,           // [B,L,H]
-    float* __restrict__ h_fin, float* __restrict__ c_fin,  // [B,H]
-    float* __restrict__ acts,            // [B,L,4H] i,g,f,o activated
-    float* __restrict__ c_prev_st,       // [B,L,H]
-    bf16raw* __restrict__ h_prev_st,   // [B,L,H]
-    float forget_bias, int B, int L, int H) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16raw* wh = reinterpret_cast<bf16raw*>(smem);
-  float* hbuf = reinterpret_cast<float*>(wh + drla_lstm_seq_wh_elems(H));
-  float* cbuf = hbuf + H;
-
-  const int b = blockIdx.x;
-  const int j = threadIdx.x;
-  const int G = 4 * H;
-
-  for (int i = j; i < H * G; i += blockDim.x) wh[i] = Wh[i];
-  if (j < H) {
-    hbuf[j] = h0[(long long)b * H + j];
-    cbuf[j] = c0[(long long)b * H + j];
-  }
-  __syncthreads();
-
-  for (int t = 0; t < L; ++t) {
-    float g = 0.0f;
-    for (int k = 0; k < H; ++k) {
-      g = fmaf(hbuf[k], lstm_b2f(wh[k * G + j]), g);
-    }
-    const long long xbase = ((long long)b * L + t) * G + j;
-    g += lstm_b2f(xg16[xbase]);
-    __shared__ float gates[LSTM_SEQ_MAX_GATES];
-    static_assert(sizeof(gates) == LSTM_SEQ_STATIC_LDS_BYTES, "LDS budget");
-    gates[j] = g;
-    __syncthreads();
-    if (j < H) {
-      const long long sb = ((long long)b * L + t) * H + j;
-      h_prev_st[sb] = drla_f32_to_bf16(hbuf[j]);
-      c_prev_st[sb] = cbuf[j];
-      const float i_s = drla_sigmoid(gates[j]);
-      const float g_t = tanhf(gates[H + j]);
-      const float f_s = drla_sigmoid(gates[2 * H + j] + forget_bias);
-      const float o_s = drla_sigmoid(gates[3 * H + j]);
-      acts[xbase] = i_s;
-      acts[((long long)b * L + t) * G + H + j] = g_t;
-      acts[((long long)b * L + t) * G + 2 * H + j] = f_s;
-      acts[((long long)b * L + t) * G + 3 * H + j] = o_s;
-      const float c_new = f_s * cbuf[j] + i_s * g_t;
-      const float h_new = o_s * tanhf(c_new);
-      h_out[sb] = h_new;
-      const float keep = done[(long long)b * L + t] ? 0.0f : 1.0f;
-      hbuf[j] = h_new * keep;
-      cbuf[j] = c_new * keep;
-    }
-    __syncthreads();
-  }
-  if (j < H) {
-    h_fin[(long long)b * H + j] = hbuf[j];
-    c_fin[(long long)b * H + j] = cbuf[j];
-  }
+    const bf16raw* __restrict__ xg16, const bf16raw* __restrict__ Wh,
+    const float* __restrict__ h0, const float* __restrict__ c0,
+    const unsigned char* __restrict__ done, float* __restrict__ h_out,
+    float* __restrict__ h_fin, float* __restrict__ c_fin,
+    float* __restrict__ acts, float* __restrict__ c_prev_st,
+    bf16raw* __restrict__ h_prev_st, float forget_bias, int B, int L,
+    int H) {
+  lstm_seq_fwd_impl<true, true>(xg16, nullptr, Wh, h0, c0, done, h_out,
+                                h_fin, c_fin, acts, c_prev_st, h_prev_st,
+                                forget_bias, L, H);
 }
 
+// One kernel over the whole backward recurrence: thread per gate, Wh in LDS.
 extern "C" __global__ void drla_lstm_seq_train_bwd(
     const float* __restrict__ dh_out,    // [B,L,H]
     const float* __restrict__ dh_fin,    // [B,H] or null
@@ -356,37 +369,18 @@ extern "C" __global__ void drla_lstm_seq_train_bwd(
   __shared__ float dg4[LSTM_SEQ_MAX_GATES];
   static_assert(sizeof(dg4) == LSTM_SEQ_STATIC_LDS_BYTES, "LDS budget");
   for (int t = L - 1; t >= 0; --t) {
-    const float keep = done[(long long)b * L + t] ? 0.0f : 1.0f;
+    const long long row = (long long)b * L + t;
+    const float keep = done[row] ? 0.0f : 1.0f;
     if (j < H) {
-      const long long ab = ((long long)b * L + t) * G;
-      const long long sb = ((long long)b * L + t) * H + j;
-      const float i_s = acts[ab + j];
-      const float g_t = acts[ab + H + j];
-      const float f_s = acts[ab + 2 * H + j];
-      const float o_s = acts[ab + 3 * H + j];
-      const float cp = c_prev_st[sb];
-      const float c_new = f_s * cp + i_s * g_t;
-      const float tc = tanhf(c_new);
-      // carry grads were stored PRE-mask; the forward applied keep_t to
-      // this step's outputs before carrying them into t+1
-      const float dh_new = dh_out[sb] + dhc[j] * keep;
-      const float d_tc = dh_new * o_s * (1.0f - tc * tc) + dcc[j] * keep;
-      const float di = d_tc * g_t;
-      const float dg = d_tc * i_s;
-      const float df = d_tc * cp;
-      const float do_ = dh_new * tc;
-      dg4[j] = di * i_s * (1.0f - i_s);
-      dg4[H + j] = dg * (1.0f - g_t * g_t);
-      dg4[2 * H + j] = df * f_s * (1.0f - f_s);
-      dg4[3 * H + j] = do_ * o_s * (1.0f - o_s);
-      dcc[j] = d_tc * f_s;  // pre-mask carry for t-1
+      lstm_seq_step_bwd(dh_out, acts, c_prev_st, dg4, dhc, dcc, keep, row, j,
+                        H);
     }
     __syncthreads();
-    dxg[((long long)b * L + t) * G + j] = drla_f32_to_bf16(dg4[j]);
+    dxg[row * G + j] = drla_f32_to_bf16(dg4[j]);
     if (j < H) {
       float s = 0.0f;
       for (int l = 0; l < G; ++l) {
-        s = fmaf(dg4[l], lstm_b2f(wh[j * G + l]), s);
+        s = fmaf(dg4[l], drla_bf16_to_f32(wh[j * G + l]), s);
       }
       dhc[j] = s;  // pre-mask carry for t-1 (h0 enters unmasked)
     }
@@ -412,18 +406,14 @@ extern "C" __global__ void drla_lstm_seq_train_bwd(
 // mask on the carry only.
 // ---------------------------------------------------------------------------
 
-template <bool STASH>
+template <bool STASH>  // parameters as lstm_seq_fwd_impl
 __device__ __forceinline__ void lstm_seq_wide_fwd_impl(
-    const bf16raw* __restrict__ xg16,  // [B,L,4H] (nullable)
-    const float* __restrict__ xg32,      // [B,L,4H] (nullable)
-    const bf16raw* __restrict__ Wh,    // [H][4H] bf16
-    const float* __restrict__ h0, const float* __restrict__ c0,  // [B,H]
-    const unsigned char* __restrict__ done,  // [B,L]
-    float* __restrict__ h_out,           // [B,L,H]
-    float* __restrict__ h_fin, float* __restrict__ c_fin,  // [B,H]
-    float* __restrict__ acts,            // [B,L,4H]  (STASH only)
-    float* __restrict__ c_prev_st,       // [B,L,H]   (STASH only)
-    bf16raw* __restrict__ h_prev_st,   // [B,L,H]   (STASH only)
+    const bf16raw* __restrict__ xg16, const float* __restrict__ xg32,
+    const bf16raw* __restrict__ Wh, const float* __restrict__ h0,
+    const float* __restrict__ c0, const unsigned char* __restrict__ done,
+    float* __restrict__ h_out, float* __restrict__ h_fin,
+    float* __restrict__ c_fin, float* __restrict__ acts,
+    float* __restrict__ c_prev_st, bf16raw* __restrict__ h_prev_st,
     float forget_bias, int L, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* gates = reinterpret_cast<float*>(smem);  // [4H]
@@ -455,33 +445,15 @@ __device__ __forceinline__ void lstm_seq_wide_fwd_impl(
         gb = fmaf(hk, __uint_as_float(u & 0xffff0000u), gb);
       }
       const long long xi = row * G + 2 * p;
-      gates[2 * p] = ga + (xg16 ? lstm_b2f(xg16[xi]) : xg32[xi]);
+      gates[2 * p] = ga + (xg16 ? drla_bf16_to_f32(xg16[xi]) : xg32[xi]);
       gates[2 * p + 1] =
-          gb + (xg16 ? lstm_b2f(xg16[xi + 1]) : xg32[xi + 1]);
+          gb + (xg16 ? drla_bf16_to_f32(xg16[xi + 1]) : xg32[xi + 1]);
     }
     __syncthreads();
     const float keep = done[row] ? 0.0f : 1.0f;
     for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
-      const long long sb = row * H + j;
-      const float i_s = drla_sigmoid(gates[j]);
-      const float g_t = tanhf(gates[H + j]);
-      const float f_s = drla_sigmoid(gates[2 * H + j] + forget_bias);
-      const float o_s = drla_sigmoid(gates[3 * H + j]);
-      const float c_old = cbuf[j];
-      if (STASH) {
-        h_prev_st[sb] = drla_f32_to_bf16(hbuf[j]);
-        c_prev_st[sb] = c_old;
-        acts[row * G + j] = i_s;
-        acts[row * G + H + j] = g_t;
-        acts[row * G + 2 * H + j] = f_s;
-        acts[row * G + 3 * H + j] = o_s;
-      }
-      const float c_new = f_s * c_old + i_s * g_t;
-      const float h_new = o_s * tanhf(c_new);
-      h_out[sb] = h_new;
-      // done-mask reset applies to the CARRY, not the emitted h
-      hbuf[j] = h_new * keep;
-      cbuf[j] = c_new * keep;
+      lstm_seq_step_fwd<STASH>(gates, hbuf, cbuf, h_out, acts, c_prev_st,
+                               h_prev_st, forget_bias, keep, row, j, H);
     }
     __syncthreads();
   }
@@ -523,16 +495,11 @@ drla_lstm_seq_wide_train_fwd(
 // (consecutive lanes on consecutive addresses), then a shuffle reduction.
 extern "C" __global__ __launch_bounds__(LSTM_SEQ_WIDE_BLOCK) void
 drla_lstm_seq_wide_train_bwd(
-    const float* __restrict__ dh_out,    // [B,L,H]
-    const float* __restrict__ dh_fin,    // [B,H] or null
-    const float* __restrict__ dc_fin,    // [B,H] or null
-    const float* __restrict__ acts,      // [B,L,4H]
-    const float* __restrict__ c_prev_st, // [B,L,H]
-    const bf16raw* __restrict__ Wh,    // [H][4H]
-    const unsigned char* __restrict__ done,  // [B,L]
-    bf16raw* __restrict__ dxg,         // [B,L,4H] gate-preact grads
-    float* __restrict__ dh0, float* __restrict__ dc0,  // [B,H]
-    int B, int L, int H) {
+    const float* __restrict__ dh_out, const float* __restrict__ dh_fin,
+    const float* __restrict__ dc_fin, const float* __restrict__ acts,
+    const float* __restrict__ c_prev_st, const bf16raw* __restrict__ Wh,
+    const unsigned char* __restrict__ done, bf16raw* __restrict__ dxg,
+    float* __restrict__ dh0, float* __restrict__ dc0, int B, int L, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* dg4 = reinterpret_cast<float*>(smem);  // [4H]
   float* dhc = dg4 + 4 * H;                     // [H]
@@ -554,28 +521,8 @@ drla_lstm_seq_wide_train_bwd(
     const long long row = (long long)b * L + t;
     const float keep = done[row] ? 0.0f : 1.0f;
     for (int j = tid; j < H; j += LSTM_SEQ_WIDE_BLOCK) {
-      const long long ab = row * G;
-      const long long sb = row * H + j;
-      const float i_s = acts[ab + j];
-      const float g_t = acts[ab + H + j];
-      const float f_s = acts[ab + 2 * H + j];
-      const float o_s = acts[ab + 3 * H + j];
-      const float cp = c_prev_st[sb];
-      const float c_new = f_s * cp + i_s * g_t;
-      const float tc = tanhf(c_new);
-      // carry grads were stored PRE-mask; the forward applied keep_t to
-      // this step's outputs before carrying them into t+1
-      const float dh_new = dh_out[sb] + dhc[j] * keep;
-      const float d_tc = dh_new * o_s * (1.0f - tc * tc) + dcc[j] * keep;
-      const float di = d_tc * g_t;
-      const float dg = d_tc * i_s;
-      const float df = d_tc * cp;
-      const float do_ = dh_new * tc;
-      dg4[j] = di * i_s * (1.0f - i_s);
-      dg4[H + j] = dg * (1.0f - g_t * g_t);
-      dg4[2 * H + j] = df * f_s * (1.0f - f_s);
-      dg4[3 * H + j] = do_ * o_s * (1.0f - o_s);
-      dcc[j] = d_tc * f_s;  // pre-mask carry for t-1
+      lstm_seq_step_bwd(dh_out, acts, c_prev_st, dg4, dhc, dcc, keep, row, j,
+                        H);
     }
     __syncthreads();
     for (int j = tid; j < G; j += LSTM_SEQ_WIDE_BLOCK) {

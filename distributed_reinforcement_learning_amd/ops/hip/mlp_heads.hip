@@ -26,11 +26,6 @@
 #define MH_PAD 8
 #define MH_LD (MH_HID + MH_PAD)
 
-__device__ __forceinline__ float mh_b2f(bf16raw u) {
-  unsigned int x = ((unsigned int)u) << 16;
-  return __uint_as_float(x);
-}
-
 // One dense pass: out[r][o] = in[r][:] . M[o][:] (+bias, ReLU / mask),
 // M [nout][kdim] row-major global, kdim = KCH * 32; rows of M at or beyond
 // nout are never read. act images [MH_BM][MH_LD] bf16.
@@ -183,11 +178,11 @@ __device__ __forceinline__ void mh_epilogue(
         const int grow = row0 + lrow;
         float v = acc[ni][r];
         if (SIDE == MH_BIAS) {
-          v += (oc < nout) ? mh_b2f(side.v[ni][r]) : 0.0f;
+          v += (oc < nout) ? drla_bf16_to_f32(side.v[ni][r]) : 0.0f;
         }
         if (RELU) v = fmaxf(v, 0.0f);
         if (SIDE == MH_MASK) {
-          const float a = (grow < N) ? mh_b2f(side.v[ni][r]) : 0.0f;
+          const float a = (grow < N) ? drla_bf16_to_f32(side.v[ni][r]) : 0.0f;
           v = (a > 0.0f) ? v : 0.0f;
         }
         if (dh_global) {
@@ -373,7 +368,7 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
     }
   } else {
     if (tid < MH_BM && row0 + tid < N) {
-      value[row0 + tid] = mh_b2f(acta[tid][0]);
+      value[row0 + tid] = drla_bf16_to_f32(acta[tid][0]);
     }
   }
 }
@@ -494,7 +489,7 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_bwd(
     if (tid < A) {
       float s = 0.0f;
       for (int r = 0; r < MH_BM; ++r) {
-        if (row0 + r < N) s += mh_b2f(dza[r][tid]);
+        if (row0 + r < N) s += drla_bf16_to_f32(dza[r][tid]);
       }
       atomicAdd(&db3p[tid], s);
     }
@@ -522,9 +517,9 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_bwd(
       const float dv = (grow < N) ? dvalue[grow] : 0.0f;
       for (int c = 0; c < 16; ++c) {
         const int ic = c0 + c;
-        float v = dv * mh_b2f(W3v[ic]);
+        float v = dv * drla_bf16_to_f32(W3v[ic]);
         if (grow < N) {
-          const float a = mh_b2f(a2v[(long long)grow * MH_HID + ic]);
+          const float a = drla_bf16_to_f32(a2v[(long long)grow * MH_HID + ic]);
           v = (a > 0.0f) ? v : 0.0f;
         } else {
           v = 0.0f;
@@ -812,7 +807,7 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_fwd(
     }
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
-      const float v = fmaxf(mh_b2f(tv[c]) + mh_b2f(bv1[c]), 0.0f);
+      const float v = fmaxf(drla_bf16_to_f32(tv[c]) + drla_bf16_to_f32(bv1[c]), 0.0f);
       const bf16raw bv = drla_f32_to_bf16(v);
       a1img[r][c0 + c] = bv;
       if (grow < N) a1stash[(long long)grow * MH_HID + c0 + c] = bv;
@@ -926,8 +921,8 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
     for (int c = 0; c < 16; ++c) {
       float v = 0.0f;
       if (grow < N) {
-        const float o = mh_b2f(ov[c]);
-        if (o > 0.0f) v = mh_b2f(dv[c]);
+        const float o = drla_bf16_to_f32(ov[c]);
+        if (o > 0.0f) v = drla_bf16_to_f32(dv[c]);
       }
       const bf16raw bv = drla_f32_to_bf16(v);
       dz2img[r][c0 + c] = bv;
@@ -969,7 +964,7 @@ extern "C" __global__ __launch_bounds__(256) void drla_embed_mlp_bwd(
         acc = 0.0f;
         cur = row;
       }
-      acc += mh_b2f(da1img[r][oc]);
+      acc += drla_bf16_to_f32(da1img[r][oc]);
     }
     if (cur >= 0) atomicAdd(&scat[(long long)cur * MH_HID + oc], acc);
   }

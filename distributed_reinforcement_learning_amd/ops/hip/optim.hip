@@ -79,11 +79,6 @@ extern "C" __global__ void drla_rmsprop_step(
 // update runs on the master and writes the rounded bf16 copy the model
 // reads — one fused HBM pass, no per-layer weight casts anywhere else.
 
-__device__ __forceinline__ float drla_bf16_to_f32(unsigned short u) {
-  unsigned int x = ((unsigned int)u) << 16;
-  return __uint_as_float(x);
-}
-
 extern "C" __global__ void drla_sq_norm_bf16(
     const unsigned short* __restrict__ x, float* __restrict__ out,
     long long n) {

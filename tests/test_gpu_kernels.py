@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from _lstm_ref import lstm_seq_reference
+
 pytestmark = pytest.mark.gpu
 
 
@@ -349,21 +351,6 @@ def test_lstm_seq_train_parity_hidden_sizes(ext, H):
     _check_lstm_seq_train(1, H, 2)
 
 
-def _lstm_seq_reference(xg, wh, h0, c0, done):
-    """fp32 torch loop on the same bf16 inputs; forget bias 1.0."""
-    h, c = h0, c0
-    outs = []
-    for t in range(xg.shape[1]):
-        gates = xg[:, t].float() + h.float() @ wh.float()
-        i, gg, f, o = gates.chunk(4, dim=1)
-        c_new = torch.sigmoid(f + 1.0) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h_new = torch.sigmoid(o) * torch.tanh(c_new)
-        outs.append(h_new)
-        keep = (~done[:, t]).float().unsqueeze(1)
-        h, c = h_new * keep, c_new * keep
-    return torch.stack(outs, dim=1), h, c
-
-
 @pytest.mark.parametrize("H", [64, 140, 256])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_lstm_seq_fwd_hidden_sizes(ext, H, dtype):
@@ -385,7 +372,7 @@ def test_lstm_seq_fwd_hidden_sizes(ext, H, dtype):
     c0 = torch.randn(B, H, device="cuda")
     done = torch.tensor([[True, False]], device="cuda")
     h_out, h_fin, c_fin = ext.lstm_seq_fwd(xg, wh, h0, c0, done, 1.0)
-    ref, h, c = _lstm_seq_reference(xg, wh, h0, c0, done)
+    ref, h, c = lstm_seq_reference(xg, wh, h0, c0, done)
     assert torch.allclose(h_out, ref, atol=2e-2, rtol=2e-2)
     assert torch.allclose(h_fin, h, atol=2e-2, rtol=2e-2)
     assert torch.allclose(c_fin, c, atol=3e-2, rtol=3e-2)
@@ -425,17 +412,7 @@ def _check_lstm_seq_train(B, H, L):
     wh2 = wh.detach().clone().requires_grad_(True)
     h02 = h0.detach().clone().requires_grad_(True)
     c02 = c0.detach().clone().requires_grad_(True)
-    h, c = h02, c02
-    outs = []
-    for t in range(L):
-        gates = xg2[:, t].float() + h.float() @ wh2.float()
-        i, gg, f, o = gates.chunk(4, dim=1)
-        c_new = torch.sigmoid(f + 1.0) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h_new = torch.sigmoid(o) * torch.tanh(c_new)
-        outs.append(h_new)
-        keep = (~done[:, t]).float().unsqueeze(1)
-        h, c = h_new * keep, c_new * keep
-    ref = torch.stack(outs, dim=1)
+    ref, h, c = lstm_seq_reference(xg2, wh2, h02, c02, done)
     (ref * g).sum().backward()
 
     assert torch.allclose(h_out, ref, atol=2e-2, rtol=2e-2)

@@ -32,6 +32,8 @@ import numpy as np
 import pytest
 import torch
 
+from _lstm_ref import lstm_seq_reference
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -42,21 +44,6 @@ def ext():
     from distributed_reinforcement_learning_amd import ops
     assert ops.available(), "HIP extension must be built on the GPU box"
     return ops.require_ext()
-
-
-def _lstm_seq_reference(xg, wh, h0, c0, done):
-    """fp32 torch loop on the same bf16 inputs; forget bias 1.0."""
-    h, c = h0, c0
-    outs = []
-    for t in range(xg.shape[1]):
-        gates = xg[:, t].float() + h.float() @ wh.float()
-        i, gg, f, o = gates.chunk(4, dim=1)
-        c_new = torch.sigmoid(f + 1.0) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h_new = torch.sigmoid(o) * torch.tanh(c_new)
-        outs.append(h_new)
-        keep = (~done[:, t]).float().unsqueeze(1)
-        h, c = h_new * keep, c_new * keep
-    return torch.stack(outs, dim=1), h, c
 
 
 def _inputs(B, H, L, seed):
@@ -103,7 +90,7 @@ def _kernel_pair(xg, wh, h0, c0, done, gs):
 def _check_train(B, H, L, done, seed=21):
     xg, wh, h0, c0, gs = _inputs(B, H, L, seed)
     got = _kernel_pair(xg, wh, h0, c0, done, gs)
-    ref = _train_pair(_lstm_seq_reference, xg, wh, h0, c0, done, gs)
+    ref = _train_pair(lstm_seq_reference, xg, wh, h0, c0, done, gs)
     errs = {k: float((got[k] - ref[k]).abs().max()) for k in TOL}
     print(f"lstm_seq_train H={H} B={B} L={L} max|err| "
           + " ".join(f"{k}={v:.2e}" for k, v in errs.items())
@@ -142,7 +129,7 @@ def test_no_grad_forward_matches_torch_loop(ext, H, dtype):
     c0 = torch.randn(B, H, device=DEV)
     done = torch.tensor([[True, False]], device=DEV)
     h_out, h_fin, c_fin = ext.lstm_seq_fwd(xg, wh, h0, c0, done, 1.0)
-    ref, h, c = _lstm_seq_reference(xg, wh, h0, c0, done)
+    ref, h, c = lstm_seq_reference(xg, wh, h0, c0, done)
     print(f"lstm_seq_fwd H={H} {dtype} max|err| "
           f"h_out={float((h_out - ref).abs().max()):.2e} "
           f"h_fin={float((h_fin - h).abs().max()):.2e} "
