@@ -281,6 +281,18 @@ torch::Tensor relu_mask_bwd(torch::Tensor dy, torch::Tensor y, int64_t CO,
   return out;
 }
 
+// the wgrad M-split in effect: DRLA_WGRAD_SPLIT (read once, for sweeps) or
+// the per-layer default from profiles/wgrad_sweep_r05.md (512 / 64 before
+// the row-major staging made a chunk cheaper)
+int conv_wgrad_split(int layer) {
+  conv_layer(layer);
+  static int split_env = [] {
+    const char* e = getenv("DRLA_WGRAD_SPLIT");
+    return e ? atoi(e) : 0;
+  }();
+  return split_env > 0 ? split_env : ((layer <= 1) ? 256 : 48);
+}
+
 std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
                                                     torch::Tensor in,
                                                     torch::Tensor dy) {
@@ -289,13 +301,7 @@ std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
   const auto& cfg = conv_layer(layer);
   const int batch = in.size(0);
   const int K = cfg.kh * cfg.kw * cfg.ci;
-  // runtime-tunable M-split (DRLA_WGRAD_SPLIT sweeps it; defaults from the
-  // on-box sweeps — atomic-free slab stores make high splits cheap)
-  static int split_env = [] {
-    const char* e = getenv("DRLA_WGRAD_SPLIT");
-    return e ? atoi(e) : 0;
-  }();
-  const int split = split_env ? split_env : ((layer <= 1) ? 512 : 64);
+  const int split = conv_wgrad_split(layer);
   // persistent zero-between-calls scratch (finalize re-zeroes on read)
   static torch::Tensor scratch_cache[4];
   if (!scratch_cache[layer].defined()) {
@@ -1443,6 +1449,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("slot") = py::none(),
         py::arg("slot_dist") = std::vector<int64_t>{});
   m.def("conv_wgrad", &conv_wgrad, "MFMA conv weight gradient (K1 bwd)");
+  m.def("_conv_wgrad_split", &conv_wgrad_split,
+        "M-split of the conv wgrad grid for a layer");
   m.def("conv_dgrad", &conv_dgrad, "MFMA conv data gradient (K1 bwd)");
   m.def("relu_mask_bwd", &relu_mask_bwd,
         "fused-ReLU backward mask + bias gradient");

@@ -22,6 +22,7 @@
 //   D: lane l, reg r -> row (l>>4)*4 + r, col l&15    (4 f32)
 
 #include "drla_kernels.h"
+#include "conv_wgrad_lds.h"
 
 // layer geometry (DRLA_CONV_GEOM), block size and tile sizes come from
 // drla_common.h, where the launch code reads the same values
@@ -424,7 +425,39 @@ extern "C" __global__ void drla_wgrad_finalize(
 // [S][K][CO] slab variant measured WORSE across the board — the S-deep
 // finalize reduce is the new bottleneck — so atomics stay; the real cost
 // is the per-chunk global-load latency chain, hence the prefetch below.)
+//
+// drla_wgrad_finalize stays a launch of its own. Folding it in (a ticket per
+// k-block after the atomics, the last block finalizing) needs an agent-scope
+// release fence in every block before its ticket, and each such fence is an
+// L2 write-back on gfx950: with one thread fencing, l1 (2048 blocks) went
+// from 26.5 to 70 us and l2/l3 lost more than the 6 us launch they saved
+// (profiles/wgrad_fold_r05.md).
 // ---------------------------------------------------------------------------
+
+// 4 u8 -> 4 bf16 of (float)u * (1/255.f), the forward's exact rounding
+__device__ __forceinline__ uint2 drla_u8x4_norm_bf16x4(unsigned int u) {
+  const float sc = 1.0f / 255.0f;
+  uint2 r;
+  r.x = drla_f32x2_to_bf16x2((float)(u & 0xFF) * sc,
+                             (float)((u >> 8) & 0xFF) * sc);
+  r.y = drla_f32x2_to_bf16x2((float)((u >> 16) & 0xFF) * sc,
+                             (float)(u >> 24) * sc);
+  return r;
+}
+
+// one 16x16x32 operand (8 bf16 per lane) from a row-major LDS tile: two
+// ds_read_b64_tr_b16, rows 8g..8g+3 at p and 8g+4..8g+7 at p + 4 rows.
+// EXEC must be all ones here (the gather crosses lanes): callers keep
+// uniform control flow around it.
+__device__ __forceinline__ bf16x8 drla_lds_tr_frag(const unsigned char* p,
+                                                   int row_bytes) {
+  typedef __attribute__((ext_vector_type(4))) short s16x4;
+  typedef __attribute__((address_space(3))) s16x4* lds_ptr;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p);
+  const s16x4 hi =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(p + 4 * row_bytes));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
 
 template <typename IN_T, int CI, int CO, int KH, int KW, int STRIDE, int HI,
           int WI, int HO, int WO>
@@ -433,27 +466,37 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
                                 float* __restrict__ scratch,     // [K][CO]
                                 int batch) {
   constexpr int K = KH * KW * CI;
-  constexpr int BKM = 64;   // m-rows per chunk (2 MFMA k-steps)
+  constexpr int BKM = DRLA_WG_ROWS;  // m-rows per chunk (2 MFMA k-steps)
   constexpr int BKK = DRLA_CONV_WGRAD_BK;  // k-cols per block
-  constexpr int PAD = 8;
   constexpr int NFRAG = CO / 16;
-  // B staging: co per thread/half
-  constexpr int CO_PER_T = (CO * 32) / DRLA_CONV_BLOCK;
+  constexpr int A_ROWB = BKK * 2;  // bytes per LDS row of the A tile
+  constexpr int B_ROWB = CO * 2;   // ... of the dY tile
+  // dY staging: 8 co (one 16-byte chunk) per thread and pass
+  constexpr int B_TPR = CO / 8;                          // threads per row
+  constexpr int B_PASSES = BKM * B_TPR / DRLA_CONV_BLOCK;  // 1 or 2
+  static_assert(K % BKK == 0, "k-blocks are full: no k range checks below");
+  static_assert(BKK == 64 && DRLA_CONV_BLOCK == 256 &&
+                    (B_PASSES == 1 || B_PASSES == 2),
+                "the maps of conv_wgrad_lds.h assume these");
   const int M = batch * HO * WO;
 
-  // Both images staged TRANSPOSED so the MFMA fragments are single
-  // ds_read_b128s, and SOFTWARE-PIPELINED: chunk m+1's global loads issue
-  // into registers while chunk m's MFMA runs — the per-chunk load-latency
-  // chain (the measured bottleneck: time scaled with M/split, not with
-  // atomics or LDS ops) overlaps compute.
+  // Both tiles are staged ROW-MAJOR, as they come from memory, with 16-byte
+  // stores, and read back column-major by ds_read_b64_tr_b16 (layout and
+  // bank analysis: conv_wgrad_lds.h). SOFTWARE-PIPELINED: chunk m+1's
+  // global loads issue into registers while chunk m's MFMA runs — the
+  // per-chunk load-latency chain (time scaled with M/split, not with
+  // atomics) overlaps compute.
   // DOUBLE-BUFFERED images: chunk t+1's LDS stores overlap chunk t's
   // MFMAs (different buffer), leaving ONE barrier per chunk instead of
   // two — with the register prefetch this removes the last serial
   // stage of the per-chunk latency chain.
-  __shared__ bf16raw Am[2][BKK][BKM + PAD];   // A image: [k][m]
-  __shared__ bf16raw BmT[2][CO][BKM + PAD];   // dY image: [co][m]
+  __shared__ __attribute__((aligned(16))) unsigned char
+      Am[2][BKM * A_ROWB];  // A image: [m][k]
+  __shared__ __attribute__((aligned(16))) unsigned char
+      Bm[2][BKM * B_ROWB];  // dY image: [m][co]
 
   const int tid = threadIdx.x;
+
   const int wave = tid / 64;
   const int lane = tid % 64;
   const int k_row0 = blockIdx.x * BKK;
@@ -501,15 +544,30 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
     a_off1 = (kk1 < K)
         ? ((long long)kh1 * WI + kwci1 / CI) * CI + (kwci1 % CI) : -1;
   }
-  const int b_lm0 = tid / (CO / CO_PER_T);
-  const int b_co0 = (tid % (CO / CO_PER_T)) * CO_PER_T;
+  const int b_lm0 = drla_wg_b_slot<CO>(tid, 0).row;
+  const int b_ch = drla_wg_b_slot<CO>(tid, 0).ch;
+  const int b_co0 = b_ch * 8;
+  constexpr int B_PASS_ROWS = drla_wg_b_slot<CO>(0, 1).row;
+
+  // LDS byte offsets (conv_wgrad_lds.h): the thread's store chunks, and its
+  // transposed-read bases for the wave's 16 k and for each co tile
+  const int a_st0 = drla_wg_chunk_off<A_ROWB>(drla_wg_a_slot(tid, 0).row,
+                                              drla_wg_a_slot(tid, 0).ch);
+  const int a_st1 = drla_wg_chunk_off<A_ROWB>(drla_wg_a_slot(tid, 1).row,
+                                              drla_wg_a_slot(tid, 1).ch);
+  const int b_st0 = drla_wg_chunk_off<B_ROWB>(b_lm0, b_ch);
+  const int a_rd = drla_wg_tr_off<A_ROWB>(lane, wave);
+  int b_rd[NFRAG];
+#pragma unroll
+  for (int ni = 0; ni < NFRAG; ++ni) {
+    b_rd[ni] = drla_wg_tr_off<B_ROWB>(lane, ni);
+  }
 
   // register prefetch state
   unsigned int ra4u_0, ra4u_1, ra4u_2, ra4u_3;
   unsigned int ra1u[4];
   bf16x8 rab0 = {0, 0, 0, 0, 0, 0, 0, 0}, rab1 = rab0;
   bf16x8 rb8_0 = rab0, rb8_1 = rab0;
-  uint2 rb4_0 = {0, 0}, rb4_1 = {0, 0};
   bool a_live = false, b_live0 = false, b_live1 = false;
 
   auto load_chunk = [&](int m0) {
@@ -552,95 +610,50 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
     const int mb0 = m0 + b_lm0;
     b_live0 = (mb0 < m_end);
     if (b_live0) {
-      if constexpr (CO_PER_T == 8) {
-        rb8_0 = *reinterpret_cast<const bf16x8*>(dy + (long long)mb0 * CO +
-                                                 b_co0);
-      } else {
-        rb4_0 = *reinterpret_cast<const uint2*>(dy + (long long)mb0 * CO +
-                                                b_co0);
-      }
+      rb8_0 = *reinterpret_cast<const bf16x8*>(dy + (long long)mb0 * CO +
+                                               b_co0);
     }
-    const int mb1 = m0 + b_lm0 + 32;
-    b_live1 = (mb1 < m_end);
-    if (b_live1) {
-      if constexpr (CO_PER_T == 8) {
+    if constexpr (B_PASSES == 2) {
+      const int mb1 = m0 + b_lm0 + B_PASS_ROWS;
+      b_live1 = (mb1 < m_end);
+      if (b_live1) {
         rb8_1 = *reinterpret_cast<const bf16x8*>(dy + (long long)mb1 * CO +
                                                  b_co0);
-      } else {
-        rb4_1 = *reinterpret_cast<const uint2*>(dy + (long long)mb1 * CO +
-                                                b_co0);
       }
     }
   };
 
   auto store_chunk = [&](int buf) {
-    bf16raw (*AmB)[BKM + PAD] = Am[buf];
-    bf16raw (*BmTB)[BKM + PAD] = BmT[buf];
-    const int lm = a_m;
+    // the thread's 16 k as two 16-byte chunks; rows past m_end are zeros
+    uint4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
     if (a_live) {
       if constexpr (CI == 4) {
-        const float sc = 1.0f / 255.0f;
-#define DRLA_WG_PUT(st, u)                                              \
-        {                                                               \
-          const int o = a_k + ((st) >> 1) * 8 + ((st) & 1) * 4;         \
-          AmB[o + 0][lm] = drla_f32_to_bf16((float)((u) & 0xFF) * sc);  \
-          AmB[o + 1][lm] =                                              \
-              drla_f32_to_bf16((float)(((u) >> 8) & 0xFF) * sc);        \
-          AmB[o + 2][lm] =                                              \
-              drla_f32_to_bf16((float)(((u) >> 16) & 0xFF) * sc);       \
-          AmB[o + 3][lm] = drla_f32_to_bf16((float)((u) >> 24) * sc);   \
-        }
-        DRLA_WG_PUT(0, ra4u_0); DRLA_WG_PUT(1, ra4u_1);
-        DRLA_WG_PUT(2, ra4u_2); DRLA_WG_PUT(3, ra4u_3);
-#undef DRLA_WG_PUT
+        const uint2 c0 = drla_u8x4_norm_bf16x4(ra4u_0);
+        const uint2 c1 = drla_u8x4_norm_bf16x4(ra4u_1);
+        const uint2 c2 = drla_u8x4_norm_bf16x4(ra4u_2);
+        const uint2 c3 = drla_u8x4_norm_bf16x4(ra4u_3);
+        a0 = {c0.x, c0.y, c1.x, c1.y};
+        a1 = {c2.x, c2.y, c3.x, c3.y};
       } else if constexpr (CI == 1) {
-        const float sc1 = 1.0f / 255.0f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const unsigned int u = ra1u[q];
-          AmB[a_k + q * 4 + 0][lm] =
-              drla_f32_to_bf16((float)(u & 0xFF) * sc1);
-          AmB[a_k + q * 4 + 1][lm] =
-              drla_f32_to_bf16((float)((u >> 8) & 0xFF) * sc1);
-          AmB[a_k + q * 4 + 2][lm] =
-              drla_f32_to_bf16((float)((u >> 16) & 0xFF) * sc1);
-          AmB[a_k + q * 4 + 3][lm] =
-              drla_f32_to_bf16((float)(u >> 24) * sc1);
-        }
+        const uint2 c0 = drla_u8x4_norm_bf16x4(ra1u[0]);
+        const uint2 c1 = drla_u8x4_norm_bf16x4(ra1u[1]);
+        const uint2 c2 = drla_u8x4_norm_bf16x4(ra1u[2]);
+        const uint2 c3 = drla_u8x4_norm_bf16x4(ra1u[3]);
+        a0 = {c0.x, c0.y, c1.x, c1.y};
+        a1 = {c2.x, c2.y, c3.x, c3.y};
       } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          AmB[a_k + e][lm] = rab0[e];
-          AmB[a_k + 8 + e][lm] = rab1[e];
-        }
+        a0 = __builtin_bit_cast(uint4, rab0);
+        a1 = __builtin_bit_cast(uint4, rab1);
       }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) AmB[a_k + t][lm] = 0;
     }
-    if constexpr (CO_PER_T == 8) {
-      const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      const bf16x8 v0 = b_live0 ? rb8_0 : z;
-      const bf16x8 v1 = b_live1 ? rb8_1 : z;
-      const int lm1 = b_lm0 + 32;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        BmTB[b_co0 + e][b_lm0] = v0[e];
-        BmTB[b_co0 + e][lm1] = v1[e];
-      }
-    } else {
-      const uint2 z = {0, 0};
-      const uint2 v0 = b_live0 ? rb4_0 : z;
-      const uint2 v1 = b_live1 ? rb4_1 : z;
-      const int lm1 = b_lm0 + 32;
-      BmTB[b_co0 + 0][b_lm0] = (bf16raw)(v0.x & 0xFFFF);
-      BmTB[b_co0 + 1][b_lm0] = (bf16raw)(v0.x >> 16);
-      BmTB[b_co0 + 2][b_lm0] = (bf16raw)(v0.y & 0xFFFF);
-      BmTB[b_co0 + 3][b_lm0] = (bf16raw)(v0.y >> 16);
-      BmTB[b_co0 + 0][lm1] = (bf16raw)(v1.x & 0xFFFF);
-      BmTB[b_co0 + 1][lm1] = (bf16raw)(v1.x >> 16);
-      BmTB[b_co0 + 2][lm1] = (bf16raw)(v1.y & 0xFFFF);
-      BmTB[b_co0 + 3][lm1] = (bf16raw)(v1.y >> 16);
+    *reinterpret_cast<uint4*>(&Am[buf][a_st0]) = a0;
+    *reinterpret_cast<uint4*>(&Am[buf][a_st1]) = a1;
+    const uint4 z = {0, 0, 0, 0};
+    *reinterpret_cast<uint4*>(&Bm[buf][b_st0]) =
+        b_live0 ? __builtin_bit_cast(uint4, rb8_0) : z;
+    if constexpr (B_PASSES == 2) {
+      *reinterpret_cast<uint4*>(&Bm[buf][b_st0 + B_PASS_ROWS * B_ROWB]) =
+          b_live1 ? __builtin_bit_cast(uint4, rb8_1) : z;
     }
   };
 
@@ -658,13 +671,16 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
       store_chunk(1 - cur);
       load_chunk(m_begin + (long long)(t + 2) * BKM);
     }
+    // uniform control flow from here to the barrier: the transposed reads
+    // need every lane (pad, don't mask)
+#pragma unroll
     for (int kk = 0; kk < BKM; kk += 32) {
-      const bf16x8 a_frag = *reinterpret_cast<const bf16x8*>(
-          &Am[cur][wave * 16 + (lane & 15)][kk + (lane >> 4) * 8]);
+      const bf16x8 a_frag =
+          drla_lds_tr_frag(&Am[cur][a_rd + kk * A_ROWB], A_ROWB);
+#pragma unroll
       for (int ni = 0; ni < NFRAG; ++ni) {
-        const int co = ni * 16 + (lane & 15);
-        const bf16x8 b_frag = *reinterpret_cast<const bf16x8*>(
-            &BmT[cur][co][kk + (lane >> 4) * 8]);
+        const bf16x8 b_frag =
+            drla_lds_tr_frag(&Bm[cur][b_rd[ni] + kk * B_ROWB], B_ROWB);
         acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_frag, b_frag,
                                                           acc[ni], 0, 0, 0);
       }
@@ -672,11 +688,14 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
     __syncthreads();
   }
 
-  for (int ni = 0; ni < NFRAG; ++ni) {
-    const int co = ni * 16 + (lane & 15);
-    for (int r = 0; r < 4; ++r) {
-      const int k = k_row0 + wave * 16 + (lane >> 4) * 4 + r;
-      if (k < K) atomicAdd(&scratch[(long long)k * CO + co], acc[ni][r]);
+  // a block whose M-slice is empty adds nothing (block-uniform)
+  if (nchunks > 0) {
+    for (int ni = 0; ni < NFRAG; ++ni) {
+      const int co = ni * 16 + (lane & 15);
+      for (int r = 0; r < 4; ++r) {
+        const int k = k_row0 + wave * 16 + (lane >> 4) * 4 + r;
+        atomicAdd(&scratch[(long long)k * CO + co], acc[ni][r]);
+      }
     }
   }
 }
