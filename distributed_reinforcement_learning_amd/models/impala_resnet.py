@@ -7,8 +7,14 @@ residual blocks, then ReLU -> flatten -> fc256, feeding the same action
 embedding + LSTM + heads as the shallow model. ~10x the conv FLOPs of the
 Atari stack — the config that stresses the gradient all-reduce.
 
-Runs channels_last on MIOpen (library conv path; the hand-written MFMA
-kernels cover the flagship Atari stack — see ops/hip/conv.hip).
+On the GPU with bf16 weights all 15 convolutions, the pre-activation ReLUs
+and the residual adds run on the hand-written MFMA 3x3 kernels
+(ops/hip/conv3x3.hip through ops/resnet_op.py), forward and backward;
+max-pool, the final ReLU and fc stay torch ops on channels_last views.
+Everywhere else (CPU actors, fp32 weights, DRLA_RESNET_CONV=0) the torso
+runs channels_last nn.Conv2d, which is also the reference of the custom
+path. The conv weights are channels_last from construction, so the custom
+path's flat [CO][9*CI] weight view is a no-copy reshape.
 """
 
 from __future__ import annotations
@@ -59,8 +65,17 @@ class ImpalaResNetTorso(nn.Module):
         # 84 -> 42 -> 21 -> 11 with pool padding 1
         self.out_features = channels[-1] * 11 * 11
         self.fc = nn.Linear(self.out_features, 256)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                m.to(memory_format=torch.channels_last)
 
     def forward(self, x_nhwc: torch.Tensor) -> torch.Tensor:
+        if x_nhwc.is_cuda:
+            from distributed_reinforcement_learning_amd.ops.resnet_op import (
+                resnet_torso, resnet_torso_ok,
+            )
+            if resnet_torso_ok(self, x_nhwc):
+                return resnet_torso(self, x_nhwc.to(torch.bfloat16))
         x = x_nhwc.to(self.fc.weight.dtype).permute(0, 3, 1, 2)
         if x.device.type == "cuda":
             x = x.contiguous(memory_format=torch.channels_last)
@@ -95,7 +110,7 @@ class ImpalaResNetActorCritic(nn.Module):
     def _features(self, state, prev_action):
         s = state
         if s.dtype == torch.uint8:
-            # ResNet torso runs the library conv path: normalize here
+            # the torso (custom or library convs) reads normalized frames
             from distributed_reinforcement_learning_amd.ops import (
                 normalize_frames,
             )

@@ -31,6 +31,7 @@ SOURCES = [
     "lstm_gates.hip",
     "optim.hip",
     "conv.hip",
+    "conv3x3.hip",
     "per_tree.hip",
     "dqn_loss.hip",
     "a2c_loss.hip",

@@ -163,10 +163,110 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
   return D;
 }
 
+// ---- 3x3 same-padding family (conv3x3.hip), layer ids 4..8 ---------------
+// kernels indexed like DRLA_CONV3_LAYERS; the first layer has no dgrad
+constexpr auto kConv3Fwd = std::array{
+    &drla_c3_fwd_4_16_84, &drla_c3_fwd_16_16_42, &drla_c3_fwd_16_32_42,
+    &drla_c3_fwd_32_32_21, &drla_c3_fwd_32_32_11};
+constexpr auto kConv3Dgrad = std::array{
+    &drla_c3_dgrad_16_16_42, &drla_c3_dgrad_16_32_42,
+    &drla_c3_dgrad_32_32_21, &drla_c3_dgrad_32_32_11};
+constexpr auto kConv3Wgrad = std::array{
+    &drla_c3_wgrad_4_16_84, &drla_c3_wgrad_16_16_42, &drla_c3_wgrad_16_32_42,
+    &drla_c3_wgrad_32_32_21, &drla_c3_wgrad_32_32_11};
+
+bool is_conv3(int layer) {
+  return layer >= DRLA_CONV3_FIRST &&
+         layer < DRLA_CONV3_FIRST + DRLA_CONV3_COUNT;
+}
+const DrlaConv3Layer& conv3_layer(int layer) {
+  TORCH_CHECK(is_conv3(layer), "bad 3x3 layer");
+  return DRLA_CONV3_LAYERS[layer - DRLA_CONV3_FIRST];
+}
+// [batch, hw, hw, c] bf16, dense; the kernels keep row counts in int and
+// element offsets in 64 bits, so the row count (plus a tile) must fit an int
+void check_conv3_tensor(const torch::Tensor& t, const DrlaConv3Layer& g,
+                        int c, const char* name) {
+  check_gpu_contig(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.dim() == 4 && t.size(1) == g.hw && t.size(2) == g.hw &&
+                  t.size(3) == c,
+              name, " must be [N, ", g.hw, ", ", g.hw, ", ", c, "]");
+  TORCH_CHECK(t.size(0) >= 1 &&
+                  t.size(0) * (int64_t)g.hw * g.hw < (int64_t(1) << 30),
+              name, ": batch out of range for the 3x3 conv kernels");
+}
+const bf16raw* conv3_opt(const c10::optional<torch::Tensor>& t,
+                         const torch::Tensor& like, const char* name) {
+  if (!t.has_value()) return nullptr;
+  check_gpu_contig(*t, name);
+  TORCH_CHECK(t->scalar_type() == torch::kBFloat16 &&
+                  t->sizes() == like.sizes(),
+              name, " must be bf16 and shaped like the output");
+  return static_cast<const bf16raw*>(t->data_ptr());
+}
+// fwd/dgrad grid: one block per 128-row tile up to the cap, then blocks walk
+// tiles grid-stride (the weight image is staged once per block)
+dim3 conv3_grid(int rows) {
+  return dim3(std::min(conv_m_tiles(rows), 4 * DRLA_MAX_BLOCKS));
+}
+
+torch::Tensor conv3_fwd(int layer, const torch::Tensor& in,
+                        const torch::Tensor& w, const torch::Tensor& bias,
+                        bool relu_in,
+                        const c10::optional<torch::Tensor>& residual) {
+  const auto& g = conv3_layer(layer);
+  check_conv3_tensor(in, g, g.ci, "in");
+  check_gpu_contig(w, "w");
+  check_gpu_contig(bias, "bias");
+  TORCH_CHECK(w.numel() == (int64_t)g.co * 9 * g.ci && bias.numel() == g.co,
+              "weight/bias do not match the layer");
+  const int batch = in.size(0);
+  auto out = torch::empty({batch, g.hw, g.hw, g.co}, in.options());
+  const bf16raw* resp = conv3_opt(residual, out, "residual");
+  hipLaunchKernelGGL(kConv3Fwd[layer - DRLA_CONV3_FIRST],
+                     conv3_grid(batch * g.hw * g.hw), dim3(DRLA_CONV_BLOCK),
+                     0, cur_stream(), BF16P(in), BF16P(w), BF16P(bias),
+                     static_cast<const bf16raw*>(nullptr), resp, BF16PM(out),
+                     batch, (int)relu_in);
+  return out;
+}
+
+torch::Tensor conv3_dgrad(int layer, const torch::Tensor& dy,
+                          const torch::Tensor& w,
+                          const c10::optional<torch::Tensor>& mask_src,
+                          const c10::optional<torch::Tensor>& addend) {
+  const auto& g = conv3_layer(layer);
+  TORCH_CHECK(layer > DRLA_CONV3_FIRST, "the first 3x3 layer has no dgrad");
+  check_conv3_tensor(dy, g, g.co, "dy");
+  check_gpu_contig(w, "w");
+  TORCH_CHECK(w.numel() == (int64_t)g.co * 9 * g.ci,
+              "weight does not match the layer");
+  const int batch = dy.size(0);
+  auto dx = torch::empty({batch, g.hw, g.hw, g.ci}, dy.options());
+  const bf16raw* maskp = conv3_opt(mask_src, dx, "mask_src");
+  const bf16raw* addp = conv3_opt(addend, dx, "addend");
+  hipLaunchKernelGGL(kConv3Dgrad[layer - DRLA_CONV3_FIRST - 1],
+                     conv3_grid(batch * g.hw * g.hw), dim3(DRLA_CONV_BLOCK),
+                     0, cur_stream(), BF16P(dy), BF16P(w),
+                     static_cast<const bf16raw*>(nullptr), maskp, addp,
+                     BF16PM(dx), batch, 0);
+  return dx;
+}
+
 std::tuple<torch::Tensor, torch::Tensor> conv_fwd(
     int layer, torch::Tensor in, torch::Tensor w, torch::Tensor bias,
     bool stash_input, c10::optional<torch::Tensor> out_slab,
-    c10::optional<torch::Tensor> slot, std::vector<int64_t> slot_dist) {
+    c10::optional<torch::Tensor> slot, std::vector<int64_t> slot_dist,
+    bool relu_in, c10::optional<torch::Tensor> residual) {
+  if (is_conv3(layer)) {
+    TORCH_CHECK(!stash_input && !out_slab.has_value() && !slot.has_value(),
+                "the 3x3 layers take no stash, slab or slot");
+    return {conv3_fwd(layer, in, w, bias, relu_in, residual),
+            torch::Tensor()};
+  }
+  TORCH_CHECK(!relu_in && !residual.has_value(),
+              "relu_in/residual are 3x3-layer options");
   check_gpu_contig(in, "in");
   TORCH_CHECK(!slot.has_value() || layer < 2,
               "only the u8 input layers take a slot");
@@ -285,17 +385,60 @@ torch::Tensor relu_mask_bwd(torch::Tensor dy, torch::Tensor y, int64_t CO,
 // the per-layer default from profiles/wgrad_sweep_r05.md (512 / 64 before
 // the row-major staging made a chunk cheaper)
 int conv_wgrad_split(int layer) {
-  conv_layer(layer);
   static int split_env = [] {
     const char* e = getenv("DRLA_WGRAD_SPLIT");
     return e ? atoi(e) : 0;
   }();
+  if (is_conv3(layer)) {
+    // 3x3 family: the fastest of a sweep at the training batch of 640
+    // frames (profiles/resnet_conv_r06.md). More blocks hide the per-chunk
+    // load latency; each block adds (9 ci + 1) * co atomics, which is what
+    // caps the split of the K = 288 layers.
+    constexpr int kSplit[DRLA_CONV3_COUNT] = {2048, 1536, 1536, 512, 256};
+    return split_env > 0 ? split_env : kSplit[layer - DRLA_CONV3_FIRST];
+  }
+  conv_layer(layer);
   return split_env > 0 ? split_env : ((layer <= 1) ? 256 : 48);
+}
+
+// 3x3 family: one scratch for all five layers. Calls are stream-ordered and
+// each finalize leaves it zero, so the next layer finds it zero.
+std::tuple<torch::Tensor, torch::Tensor> conv3_wgrad(int layer,
+                                                     const torch::Tensor& in,
+                                                     const torch::Tensor& dy,
+                                                     bool relu_in) {
+  const auto& g = conv3_layer(layer);
+  check_conv3_tensor(in, g, g.ci, "in");
+  check_conv3_tensor(dy, g, g.co, "dy");
+  TORCH_CHECK(in.size(0) == dy.size(0), "in and dy differ in batch");
+  const int batch = in.size(0);
+  const int K = 9 * g.ci;
+  static torch::Tensor scratch;
+  if (!scratch.defined()) {
+    scratch = torch::zeros({DRLA_CONV3_SCRATCH_ELEMS},
+                           dy.options().dtype(torch::kFloat));
+  }
+  TORCH_CHECK((K + 1) * g.co <= DRLA_CONV3_SCRATCH_ELEMS, "scratch too small");
+  hipLaunchKernelGGL(kConv3Wgrad[layer - DRLA_CONV3_FIRST],
+                     dim3(conv_wgrad_split(layer)), dim3(DRLA_CONV_BLOCK), 0,
+                     cur_stream(), BF16P(in), BF16P(dy),
+                     scratch.data_ptr<float>(), batch, (int)relu_in);
+  auto dw = torch::empty({g.co, K}, dy.options());
+  auto dbias = torch::empty({g.co}, dy.options());
+  hipLaunchKernelGGL(drla_c3_wgrad_finalize,
+                     dim3(drla_grid((long long)(K + 1) * g.co)),
+                     dim3(DRLA_BLOCK), 0, cur_stream(),
+                     scratch.data_ptr<float>(), BF16PM(dw), BF16PM(dbias), K,
+                     g.co);
+  return {dw, dbias};
 }
 
 std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
                                                     torch::Tensor in,
-                                                    torch::Tensor dy) {
+                                                    torch::Tensor dy,
+                                                    bool relu_in) {
+  if (is_conv3(layer)) return conv3_wgrad(layer, in, dy, relu_in);
+  TORCH_CHECK(!relu_in, "relu_in is a 3x3-layer option");
   check_gpu_contig(in, "in");
   check_gpu_contig(dy, "dy");
   const auto& cfg = conv_layer(layer);
@@ -330,7 +473,12 @@ std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
   return {dw, dbias};
 }
 
-torch::Tensor conv_dgrad(int layer, torch::Tensor dy, torch::Tensor w) {
+torch::Tensor conv_dgrad(int layer, torch::Tensor dy, torch::Tensor w,
+                         c10::optional<torch::Tensor> mask_src,
+                         c10::optional<torch::Tensor> addend) {
+  if (is_conv3(layer)) return conv3_dgrad(layer, dy, w, mask_src, addend);
+  TORCH_CHECK(!mask_src.has_value() && !addend.has_value(),
+              "mask_src/addend are 3x3-layer options");
   check_gpu_contig(dy, "dy");
   check_gpu_contig(w, "w");
   TORCH_CHECK(layer == 2 || layer == 3, "dgrad only for l2/l3");
@@ -1447,11 +1595,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("layer"), py::arg("x"), py::arg("w"), py::arg("bias"),
         py::arg("stash_input"), py::arg("out_slab") = py::none(),
         py::arg("slot") = py::none(),
-        py::arg("slot_dist") = std::vector<int64_t>{});
-  m.def("conv_wgrad", &conv_wgrad, "MFMA conv weight gradient (K1 bwd)");
+        py::arg("slot_dist") = std::vector<int64_t>{},
+        py::arg("relu_in") = false, py::arg("residual") = py::none());
+  m.def("conv_wgrad", &conv_wgrad,
+        "MFMA conv weight + bias gradient (K1 bwd; layers 4..8: 3x3 family)",
+        py::arg("layer"), py::arg("x"), py::arg("dy"),
+        py::arg("relu_in") = false);
   m.def("_conv_wgrad_split", &conv_wgrad_split,
         "M-split of the conv wgrad grid for a layer");
-  m.def("conv_dgrad", &conv_dgrad, "MFMA conv data gradient (K1 bwd)");
+  m.def("conv_dgrad", &conv_dgrad, "MFMA conv data gradient (K1 bwd)",
+        py::arg("layer"), py::arg("dy"), py::arg("w"),
+        py::arg("mask_src") = py::none(), py::arg("addend") = py::none());
   m.def("relu_mask_bwd", &relu_mask_bwd,
         "fused-ReLU backward mask + bias gradient");
   m.def("dqn_loss_fwd", &dqn_loss_fwd,

@@ -43,6 +43,23 @@ constexpr DrlaConvLayer DRLA_CONV_LAYERS[4] = {
 #define DRLA_CONV_BM 128       // fwd/dgrad rows per block (grid.x = M / BM)
 #define DRLA_CONV_WGRAD_BK 64  // wgrad k-rows per block (grid.x = K / BK)
 
+// 3x3 / stride 1 / zero padding 1 family of the IMPALA ResNet torso
+// (conv3x3.hip). The Python layer ids continue DRLA_CONV_LAYERS: id =
+// DRLA_CONV3_FIRST + row. Square images, hw = H = W in and out.
+struct DrlaConv3Layer { int ci, co, hw; };
+#define DRLA_CONV3_FIRST 4
+#define DRLA_CONV3_COUNT 5
+constexpr DrlaConv3Layer DRLA_CONV3_LAYERS[DRLA_CONV3_COUNT] = {
+    {4, 16, 84},   // 4: section 1 conv
+    {16, 16, 42},  // 5: section 1 residual blocks
+    {16, 32, 42},  // 6: section 2 conv
+    {32, 32, 21},  // 7: section 2 residual blocks, section 3 conv
+    {32, 32, 11},  // 8: section 3 residual blocks
+};
+#define DRLA_CONV3_WGRAD_ROWS 64  // wgrad m-rows per chunk
+// wgrad scratch: [9*ci + 1][co] f32, the last row is the bias gradient
+constexpr int DRLA_CONV3_SCRATCH_ELEMS = (9 * 32 + 1) * 32;
+
 // fused V-trace loss: T sizes the LDS scan buffers, A is the softmax width
 #define VT_MAX_T 128
 #define VT_MAX_A 64

@@ -126,6 +126,39 @@ DRLA_KERNEL drla_conv_dgrad_l2(const bf16raw*, const bf16raw*, bf16raw*,
 DRLA_KERNEL drla_conv_dgrad_l3(const bf16raw*, const bf16raw*, bf16raw*,
                                int);
 
+// ---- conv3x3.hip (geometry order = DRLA_CONV3_LAYERS) ---------------------
+// fwd and dgrad: in, w, bias, mask, residual/addend, out, batch, relu_in
+DRLA_KERNEL drla_c3_fwd_4_16_84(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_fwd_16_16_42(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_fwd_16_32_42(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_fwd_32_32_21(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_fwd_32_32_11(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_dgrad_16_16_42(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_dgrad_16_32_42(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_dgrad_32_32_21(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+DRLA_KERNEL drla_c3_dgrad_32_32_11(const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, bf16raw*, int, int);
+// wgrad: in, dy, scratch, batch, relu_in
+DRLA_KERNEL drla_c3_wgrad_4_16_84(const bf16raw*, const bf16raw*, float*,
+    int, int);
+DRLA_KERNEL drla_c3_wgrad_16_16_42(const bf16raw*, const bf16raw*, float*,
+    int, int);
+DRLA_KERNEL drla_c3_wgrad_16_32_42(const bf16raw*, const bf16raw*, float*,
+    int, int);
+DRLA_KERNEL drla_c3_wgrad_32_32_21(const bf16raw*, const bf16raw*, float*,
+    int, int);
+DRLA_KERNEL drla_c3_wgrad_32_32_11(const bf16raw*, const bf16raw*, float*,
+    int, int);
+DRLA_KERNEL drla_c3_wgrad_finalize(float*, bf16raw*, bf16raw*, int, int);
+
 // ---- per_tree.hip ---------------------------------------------------------
 DRLA_KERNEL drla_per_update(float*, const long long*, const float*, int,
                             long long);
