@@ -143,6 +143,8 @@ constexpr auto kConvWgradU8 =
     std::array{&drla_conv_wgrad_l1, &drla_conv_wgrad_l1_c1};
 constexpr auto kConvWgradBf16 =
     std::array{&drla_conv_wgrad_l2, &drla_conv_wgrad_l3};
+constexpr auto kConvDgrad =
+    std::array{&drla_conv_dgrad_l2, &drla_conv_dgrad_l3};
 
 const DrlaConvLayer& conv_layer(int layer) {
   TORCH_CHECK(layer >= 0 && layer < 4, "bad layer");
@@ -486,19 +488,13 @@ torch::Tensor conv_dgrad(int layer, torch::Tensor dy, torch::Tensor w,
   const int batch = dy.size(0);
   auto dx = torch::empty({batch, cfg.hi, cfg.wi, cfg.ci},
                          dy.options().dtype(torch::kBFloat16));
-  if (layer == 2) {
-    // parity-class kernel: blockIdx.y = (hi%2, wi%2) class, each class
-    // covers batch * (hi/2) * (wi/2) rows
-    const int grid_c = conv_m_tiles(batch * (cfg.hi / 2) * (cfg.wi / 2));
-    hipLaunchKernelGGL(drla_conv_dgrad_l2, dim3(grid_c, 4),
-                       dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(dy),
-                       BF16P(w), BF16PM(dx), batch);
-  } else {
-    hipLaunchKernelGGL(drla_conv_dgrad_l3,
-                       dim3(conv_m_tiles(batch * cfg.hi * cfg.wi)),
-                       dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(dy),
-                       BF16P(w), BF16PM(dx), batch);
-  }
+  // blockIdx.y = the (hi % s, wi % s) class, batch * (hi/s) * (wi/s) rows each
+  const int s = cfg.stride;
+  hipLaunchKernelGGL(
+      kConvDgrad[layer - 2],
+      dim3(conv_m_tiles(batch * (cfg.hi / s) * (cfg.wi / s)), s * s),
+      dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(dy), BF16P(w), BF16PM(dx),
+      batch);
   return dx;
 }
 

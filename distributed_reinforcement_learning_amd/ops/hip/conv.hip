@@ -20,14 +20,17 @@
 //   A: lane l holds A[l&15][(l>>4)*8 + e], e = 0..7   (8 bf16 = 4 VGPRs)
 //   B: lane l holds B[(l>>4)*8 + e][l&15]             (8 bf16)
 //   D: lane l, reg r -> row (l>>4)*4 + r, col l&15    (4 f32)
+//
+// Three bodies: conv_fwd_impl, conv_wgrad_impl and ONE conv_dgrad_impl for
+// both strides (residue classes of the input pixel; stride 1 is the one-class
+// case). Shared with conv3x3.hip through conv_tile.h: CONV_KERNEL, the u8
+// load + normalize pair both u8 kernels stage with, the transposed LDS
+// fragment read of the wgrad, and the MFMA step over the padded tiles that
+// forward and dgrad run. The wgrad's LDS maps stay in conv_wgrad_lds.h.
 
 #include "drla_kernels.h"
+#include "conv_tile.h"
 #include "conv_wgrad_lds.h"
-
-// layer geometry (DRLA_CONV_GEOM), block size and tile sizes come from
-// drla_common.h, where the launch code reads the same values
-#define CONV_KERNEL \
-  extern "C" __global__ __launch_bounds__(DRLA_CONV_BLOCK) void
 
 // ---------------------------------------------------------------------------
 // layout probe: D = A @ B for one 16x16x32 tile, used by tests to pin the
@@ -105,9 +108,9 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
   // software-pipelined K-loop: chunk k0+BK's global loads issue into
   // registers while chunk k0's MFMA runs (same structure as the wgrad —
   // the per-chunk load-latency chain is what sets kernel time here)
-  unsigned int ra4u_0, ra4u_1, ra4u_2, ra4u_3;
-  unsigned int ra1u[4];
-  bf16x8 rab0 = {0, 0, 0, 0, 0, 0, 0, 0}, rab1 = rab0;
+  constexpr bool U8 = sizeof(IN_T) == 1;
+  // u8: ra0 holds the 16 raw bytes
+  bf16x8 ra0 = {0, 0, 0, 0, 0, 0, 0, 0}, ra1 = ra0;
   uint4 rbw4;
   uint2 rbw2;
   constexpr int THREADS_PER_CO = DRLA_CONV_BLOCK / CO;  // 8 (CO=32) or 4
@@ -117,39 +120,19 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
 
   auto load_chunk = [&](int k0) {
     if (gm < M) {
-      if constexpr (CI == 4) {
-        // the thread's 4 taps share kh and have CONSECUTIVE kw (16
-        // k-values = 4 taps x 4 ci; tap0 % 8 is always 0 or 4), so the
-        // four uchar4 gathers are 16 contiguous 16 B-aligned bytes
-        const int kk = k0 + a_k0;
-        const int kh = kk / (KW * CI);
-        const int kw = (kk - kh * KW * CI) / CI;
-        const uint4 packed = *reinterpret_cast<const uint4*>(
-            in + (in_base + (long long)kh * WI + kw) * CI);
-        ra4u_0 = packed.x; ra4u_1 = packed.y;
-        ra4u_2 = packed.z; ra4u_3 = packed.w;
-      } else if constexpr (CI == 1) {
-        // 16 consecutive k = two full kw rows of 8 contiguous bytes
-        // (4-byte aligned): 4 uint loads instead of 16 ubyte gathers
-        const int kh0 = (k0 + a_k0) / KW;
-#pragma unroll
-        for (int rrow = 0; rrow < 2; ++rrow) {
-          const unsigned char* src =
-              in + in_base + (long long)(kh0 + rrow) * WI;
-          ra1u[rrow * 2 + 0] = *reinterpret_cast<const unsigned int*>(src);
-          ra1u[rrow * 2 + 1] =
-              *reinterpret_cast<const unsigned int*>(src + 4);
-        }
+      // the thread's 16 k share kh (CI == 1: two kh rows) and are contiguous
+      // in memory from (kh, kw, ci)
+      const int kk = k0 + a_k0;
+      const int kh = kk / (KW * CI);
+      const int kwci = kk - kh * KW * CI;
+      const int kw = kwci / CI;
+      const int ci = kwci - kw * CI;
+      const IN_T* src = in + (in_base + (long long)kh * WI + kw) * CI + ci;
+      if constexpr (U8) {
+        ra0 = drla_u8x16_load<CI, WI>(src);
       } else {
-        const int kk = k0 + a_k0;
-        const int kh = kk / (KW * CI);
-        const int kwci = kk - kh * KW * CI;
-        const int kw = kwci / CI;
-        const int ci = kwci - kw * CI;
-        const bf16raw* src = reinterpret_cast<const bf16raw*>(in) +
-                             (in_base + (long long)kh * WI + kw) * CI + ci;
-        rab0 = *reinterpret_cast<const bf16x8*>(src);
-        rab1 = *reinterpret_cast<const bf16x8*>(src + 8);
+        ra0 = *reinterpret_cast<const bf16x8*>(src);
+        ra1 = *reinterpret_cast<const bf16x8*>(src + 8);
       }
     }
     const bf16raw* src = w + (long long)b_co * K + k0 + b_kpart;
@@ -161,40 +144,13 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
   };
 
   auto store_chunk = [&]() {
+    // rows past M are zeros. A branch, not a select of the two values: with
+    // the select the bf16 layers allocate 70 + 32 registers instead of 48 + 48
     if (gm < M) {
-      if constexpr (CI == 4) {
-        const float sc = 1.0f / 255.0f;
-#define DRLA_CF_PUT(t, u)                                               \
-        {                                                               \
-          const int o = a_k0 + (t) * 4;                                 \
-          Abuf[a_row][o + 0] = drla_f32_to_bf16((float)((u) & 0xFF) * sc); \
-          Abuf[a_row][o + 1] =                                          \
-              drla_f32_to_bf16((float)(((u) >> 8) & 0xFF) * sc);        \
-          Abuf[a_row][o + 2] =                                          \
-              drla_f32_to_bf16((float)(((u) >> 16) & 0xFF) * sc);       \
-          Abuf[a_row][o + 3] = drla_f32_to_bf16((float)((u) >> 24) * sc); \
-        }
-        DRLA_CF_PUT(0, ra4u_0); DRLA_CF_PUT(1, ra4u_1);
-        DRLA_CF_PUT(2, ra4u_2); DRLA_CF_PUT(3, ra4u_3);
-#undef DRLA_CF_PUT
-      } else if constexpr (CI == 1) {
-        const float sc = 1.0f / 255.0f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const unsigned int u = ra1u[q];
-          Abuf[a_row][a_k0 + q * 4 + 0] =
-              drla_f32_to_bf16((float)(u & 0xFF) * sc);
-          Abuf[a_row][a_k0 + q * 4 + 1] =
-              drla_f32_to_bf16((float)((u >> 8) & 0xFF) * sc);
-          Abuf[a_row][a_k0 + q * 4 + 2] =
-              drla_f32_to_bf16((float)((u >> 16) & 0xFF) * sc);
-          Abuf[a_row][a_k0 + q * 4 + 3] =
-              drla_f32_to_bf16((float)(u >> 24) * sc);
-        }
-      } else {
-        *reinterpret_cast<bf16x8*>(&Abuf[a_row][a_k0]) = rab0;
-        *reinterpret_cast<bf16x8*>(&Abuf[a_row][a_k0 + 8]) = rab1;
-      }
+      bf16x8 a0 = ra0, a1 = ra1;
+      if constexpr (U8) drla_u8x16_norm_bf16x16(ra0, a0, a1);
+      *reinterpret_cast<bf16x8*>(&Abuf[a_row][a_k0]) = a0;
+      *reinterpret_cast<bf16x8*>(&Abuf[a_row][a_k0 + 8]) = a1;
     } else {
       for (int t = 0; t < 16; t += 8) {
         *reinterpret_cast<uint4*>(&Abuf[a_row][a_k0 + t]) = uint4{0, 0, 0, 0};
@@ -207,23 +163,15 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
     }
   };
 
+  // fully unrolled: every step's (kh, kw, ci) decode folds to constants
   load_chunk(0);
+#pragma unroll
   for (int k0 = 0; k0 < K; k0 += BK) {
     store_chunk();
     __syncthreads();
     if (k0 + BK < K) load_chunk(k0 + BK);
-    // ---- MFMA: wave covers rows [wave*32, wave*32+32) x CO ----
-    for (int mi = 0; mi < 2; ++mi) {
-      const int arow = wave * 32 + mi * 16 + (lane & 15);
-      const bf16x8 a_frag =
-          *reinterpret_cast<const bf16x8*>(&Abuf[arow][(lane >> 4) * 8]);
-      for (int ni = 0; ni < NFRAG; ++ni) {
-        const bf16x8 b_frag = *reinterpret_cast<const bf16x8*>(
-            &Bbuf[ni * 16 + (lane & 15)][(lane >> 4) * 8]);
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a_frag, b_frag, acc[mi][ni], 0, 0, 0);
-      }
-    }
+    // wave covers rows [wave*32, wave*32+32) x CO
+    drla_mfma_step_kmajor<NFRAG>(Abuf, Bbuf, wave, lane, acc);
     __syncthreads();
   }
 
@@ -264,10 +212,6 @@ __device__ void conv_fwd_impl(const IN_T* __restrict__ in,
     }
   }
 }
-
-// b_frag reads above: B fragment needs B[k][col] where the LDS image is
-// Bbuf[co][k] — i.e. we feed mfma(A, B^T-read) which computes A @ B with
-// B[k][col] = Bbuf[col][k]. The probe/parity tests pin this down.
 
 CONV_KERNEL drla_conv_fwd_l1(
     const unsigned char* in, const bf16raw* w, const bf16raw* bias,
@@ -434,31 +378,6 @@ extern "C" __global__ void drla_wgrad_finalize(
 // (profiles/wgrad_fold_r05.md).
 // ---------------------------------------------------------------------------
 
-// 4 u8 -> 4 bf16 of (float)u * (1/255.f), the forward's exact rounding
-__device__ __forceinline__ uint2 drla_u8x4_norm_bf16x4(unsigned int u) {
-  const float sc = 1.0f / 255.0f;
-  uint2 r;
-  r.x = drla_f32x2_to_bf16x2((float)(u & 0xFF) * sc,
-                             (float)((u >> 8) & 0xFF) * sc);
-  r.y = drla_f32x2_to_bf16x2((float)((u >> 16) & 0xFF) * sc,
-                             (float)(u >> 24) * sc);
-  return r;
-}
-
-// one 16x16x32 operand (8 bf16 per lane) from a row-major LDS tile: two
-// ds_read_b64_tr_b16, rows 8g..8g+3 at p and 8g+4..8g+7 at p + 4 rows.
-// EXEC must be all ones here (the gather crosses lanes): callers keep
-// uniform control flow around it.
-__device__ __forceinline__ bf16x8 drla_lds_tr_frag(const unsigned char* p,
-                                                   int row_bytes) {
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4* lds_ptr;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p);
-  const s16x4 hi =
-      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(p + 4 * row_bytes));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 template <typename IN_T, int CI, int CO, int KH, int KW, int STRIDE, int HI,
           int WI, int HO, int WO>
 __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
@@ -508,42 +427,20 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
   const int m_begin = blockIdx.y * m_per_split;
   const int m_end = min(M, m_begin + m_per_split);
 
-  // staging assignment: thread t -> A row t>>2 with k-chunk (t&3)*16; the
-  // k-position decode is m-invariant, so tap offsets precompute once
+  // staging assignment: thread t -> A row t>>2 with k-chunk (t&3)*16. The
+  // element offset of a k from the row's first input element is m-invariant
+  // and precomputed once: the u8 layers load their 16 k from a_off0 alone
+  // (drla_u8x16_load), the bf16 layers as two 8-k chunks, which may lie on
+  // different kernel rows
   const int a_m = tid >> 2;
   const int a_k = (tid & 3) * 16;
-  long long a_off0 = 0, a_off1 = 0;
-  long long a_offc[16];
-  if constexpr (CI == 4) {
-    // the thread's 4 taps are pixel-consecutive within one kh row
-    // (tap0 % 8 is 0 or 4), so one base offset covers the uint4 load
-    const int kb = k_row0 + a_k;
-    const int kh = kb / (KW * CI);
-    a_off0 = (long long)kh * WI + (kb - kh * KW * CI) / CI;
-  } else if constexpr (CI == 1) {
-    // the contiguous uint row loads below read all 16 taps without a
-    // per-tap range check — only sound when every k-block is fully
-    // in-range (the 8x8x1 instantiation: K=64 fills one BKK block)
-    static_assert(K % BKK == 0,
-                  "CI==1 contiguous row staging requires K % BKK == 0");
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const int k2 = k_row0 + a_k + t;
-      const int kh = k2 / KW;
-      a_offc[t] = (k2 < K) ? (long long)kh * WI + (k2 - kh * KW) : -1;
-    }
-  } else {
-    const int kk0 = k_row0 + a_k;
-    const int kh0 = kk0 / (KW * CI);
-    const int kwci0 = kk0 - kh0 * KW * CI;
-    a_off0 = (kk0 < K)
-        ? ((long long)kh0 * WI + kwci0 / CI) * CI + (kwci0 % CI) : -1;
-    const int kk1 = kk0 + 8;
-    const int kh1 = kk1 / (KW * CI);
-    const int kwci1 = kk1 - kh1 * KW * CI;
-    a_off1 = (kk1 < K)
-        ? ((long long)kh1 * WI + kwci1 / CI) * CI + (kwci1 % CI) : -1;
-  }
+  constexpr bool U8 = sizeof(IN_T) == 1;
+  auto k_off = [](int k) {
+    const int kh = k / (KW * CI);
+    return (long long)kh * WI * CI + (k - kh * KW * CI);
+  };
+  const long long a_off0 = k_off(k_row0 + a_k);
+  const long long a_off1 = k_off(k_row0 + a_k + 8);
   const int b_lm0 = drla_wg_b_slot<CO>(tid, 0).row;
   const int b_ch = drla_wg_b_slot<CO>(tid, 0).ch;
   const int b_co0 = b_ch * 8;
@@ -563,11 +460,9 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
     b_rd[ni] = drla_wg_tr_off<B_ROWB>(lane, ni);
   }
 
-  // register prefetch state
-  unsigned int ra4u_0, ra4u_1, ra4u_2, ra4u_3;
-  unsigned int ra1u[4];
-  bf16x8 rab0 = {0, 0, 0, 0, 0, 0, 0, 0}, rab1 = rab0;
-  bf16x8 rb8_0 = rab0, rb8_1 = rab0;
+  // register prefetch state; u8: ra0 holds the 16 raw bytes
+  bf16x8 ra0 = {0, 0, 0, 0, 0, 0, 0, 0}, ra1 = ra0;
+  bf16x8 rb0 = ra0, rb1 = ra0;
   bool a_live = false, b_live0 = false, b_live1 = false;
 
   auto load_chunk = [&](int m0) {
@@ -578,82 +473,48 @@ __device__ void conv_wgrad_impl(const IN_T* __restrict__ in,
       const int rem = m - n_idx * (HO * WO);
       const int ho = rem / WO;
       const int wo = rem - ho * WO;
-      const long long base =
-          ((long long)n_idx * HI + ho * STRIDE) * WI + wo * STRIDE;
-      if constexpr (CI == 4) {
-        // taps 0..3 of this thread share kh with consecutive kw (see the
-        // fwd note): one contiguous 16 B-aligned uint4 replaces the four
-        // uchar4 gathers
-        const uint4 packed = *reinterpret_cast<const uint4*>(
-            in + (base + a_off0) * CI);
-        ra4u_0 = packed.x; ra4u_1 = packed.y;
-        ra4u_2 = packed.z; ra4u_3 = packed.w;
-      } else if constexpr (CI == 1) {
-        // two contiguous 8-byte kw rows (see the fwd note)
-#pragma unroll
-        for (int rrow = 0; rrow < 2; ++rrow) {
-          const unsigned char* src = in + base + a_offc[rrow * 8];
-          ra1u[rrow * 2 + 0] = *reinterpret_cast<const unsigned int*>(src);
-          ra1u[rrow * 2 + 1] =
-              *reinterpret_cast<const unsigned int*>(src + 4);
-        }
+      const IN_T* src =
+          in + (((long long)n_idx * HI + ho * STRIDE) * WI + wo * STRIDE) * CI;
+      if constexpr (U8) {
+        ra0 = drla_u8x16_load<CI, WI>(src + a_off0);
       } else {
-        const bf16raw* inb = reinterpret_cast<const bf16raw*>(in);
-        if (a_off0 >= 0) {
-          rab0 = *reinterpret_cast<const bf16x8*>(inb + base * CI + a_off0);
-        }
-        if (a_off1 >= 0) {
-          rab1 = *reinterpret_cast<const bf16x8*>(inb + base * CI + a_off1);
-        }
+        ra0 = *reinterpret_cast<const bf16x8*>(src + a_off0);
+        ra1 = *reinterpret_cast<const bf16x8*>(src + a_off1);
       }
     }
     const int mb0 = m0 + b_lm0;
     b_live0 = (mb0 < m_end);
     if (b_live0) {
-      rb8_0 = *reinterpret_cast<const bf16x8*>(dy + (long long)mb0 * CO +
-                                               b_co0);
+      rb0 = *reinterpret_cast<const bf16x8*>(dy + (long long)mb0 * CO + b_co0);
     }
     if constexpr (B_PASSES == 2) {
       const int mb1 = m0 + b_lm0 + B_PASS_ROWS;
       b_live1 = (mb1 < m_end);
       if (b_live1) {
-        rb8_1 = *reinterpret_cast<const bf16x8*>(dy + (long long)mb1 * CO +
-                                                 b_co0);
+        rb1 = *reinterpret_cast<const bf16x8*>(dy + (long long)mb1 * CO +
+                                              b_co0);
       }
     }
   };
 
   auto store_chunk = [&](int buf) {
     // the thread's 16 k as two 16-byte chunks; rows past m_end are zeros
-    uint4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+    bf16x8 a0 = {0, 0, 0, 0, 0, 0, 0, 0}, a1 = a0;
     if (a_live) {
-      if constexpr (CI == 4) {
-        const uint2 c0 = drla_u8x4_norm_bf16x4(ra4u_0);
-        const uint2 c1 = drla_u8x4_norm_bf16x4(ra4u_1);
-        const uint2 c2 = drla_u8x4_norm_bf16x4(ra4u_2);
-        const uint2 c3 = drla_u8x4_norm_bf16x4(ra4u_3);
-        a0 = {c0.x, c0.y, c1.x, c1.y};
-        a1 = {c2.x, c2.y, c3.x, c3.y};
-      } else if constexpr (CI == 1) {
-        const uint2 c0 = drla_u8x4_norm_bf16x4(ra1u[0]);
-        const uint2 c1 = drla_u8x4_norm_bf16x4(ra1u[1]);
-        const uint2 c2 = drla_u8x4_norm_bf16x4(ra1u[2]);
-        const uint2 c3 = drla_u8x4_norm_bf16x4(ra1u[3]);
-        a0 = {c0.x, c0.y, c1.x, c1.y};
-        a1 = {c2.x, c2.y, c3.x, c3.y};
+      if constexpr (U8) {
+        drla_u8x16_norm_bf16x16(ra0, a0, a1);
       } else {
-        a0 = __builtin_bit_cast(uint4, rab0);
-        a1 = __builtin_bit_cast(uint4, rab1);
+        a0 = ra0;
+        a1 = ra1;
       }
     }
-    *reinterpret_cast<uint4*>(&Am[buf][a_st0]) = a0;
-    *reinterpret_cast<uint4*>(&Am[buf][a_st1]) = a1;
-    const uint4 z = {0, 0, 0, 0};
-    *reinterpret_cast<uint4*>(&Bm[buf][b_st0]) =
-        b_live0 ? __builtin_bit_cast(uint4, rb8_0) : z;
+    *reinterpret_cast<bf16x8*>(&Am[buf][a_st0]) = a0;
+    *reinterpret_cast<bf16x8*>(&Am[buf][a_st1]) = a1;
+    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    *reinterpret_cast<bf16x8*>(&Bm[buf][b_st0]) = b_live0 ? rb0 : z;
     if constexpr (B_PASSES == 2) {
-      *reinterpret_cast<uint4*>(&Bm[buf][b_st0 + B_PASS_ROWS * B_ROWB]) =
-          b_live1 ? __builtin_bit_cast(uint4, rb8_1) : z;
+      *reinterpret_cast<bf16x8*>(&Bm[buf][b_st0 + B_PASS_ROWS * B_ROWB]) =
+          b_live1 ? rb1 : z;
     }
   };
 
@@ -720,24 +581,38 @@ CONV_KERNEL drla_conv_wgrad_l3(
 // ---------------------------------------------------------------------------
 // dgrad: dX[n,hi,wi,ci] = sum_{kh,kw,co valid} dY[n,ho',wo',co] *
 //        W[co][(kh*KW+kw)*CI+ci],  ho' = (hi-kh)/STRIDE (when integral).
-// Implicit GEMM: M2 = N*HI*WI rows, Kg = KH*KW*CO, CI cols.
+//
+// Residue classes: for a fixed (ph, pw) = (hi % STRIDE, wi % STRIDE) only the
+// taps kh = ph + STRIDE*i, kw = pw + STRIDE*j can contribute, and for those
+// ho' = hi/STRIDE - i exactly. Blocks are grouped by class (blockIdx.y), so a
+// block walks just the live taps and stages no zeros for dead ones: 4 of 16
+// taps for the stride-2 layer, and for stride 1 the one class with every tap.
+// Implicit GEMM per class: batch * (HI/STRIDE) * (WI/STRIDE) rows, CI cols,
+// reduction over (live tap, co) in steps of one tap x 32 co.
 // ---------------------------------------------------------------------------
 
 template <int CI, int CO, int KH, int KW, int STRIDE, int HI, int WI, int HO,
           int WO>
 __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
                                 const bf16raw* __restrict__ w,   // [CO][K]
-                                bf16raw* __restrict__ dx,        // [M2][CI]
+                                bf16raw* __restrict__ dx,  // [N][HI][WI][CI]
                                 int batch) {
   constexpr int K = KH * KW * CI;
-  constexpr int Kg = KH * KW * CO;
   constexpr int BM = DRLA_CONV_BM;
-  constexpr int BK = 32;   // kg per step: one tap x 32 co
+  constexpr int BK = 32;   // one tap x 32 co per step
   constexpr int PAD = 8;
   constexpr int NFRAG = CI / 16;
-  const int M2 = batch * HI * WI;
+  constexpr int HC = HI / STRIDE, WC = WI / STRIDE;  // pixels of a class
+  constexpr int TH = KH / STRIDE, TW = KW / STRIDE;  // live taps of a class
+  constexpr int NSTEPS = TH * TW * (CO / BK);
+  static_assert(KH % STRIDE == 0 && KW % STRIDE == 0 && HI % STRIDE == 0 &&
+                    WI % STRIDE == 0,
+                "every class has the same taps and the same pixel count");
+  static_assert(CO % BK == 0, "a step is 32 co of one tap");
+  const int ph = blockIdx.y / STRIDE, pw = blockIdx.y % STRIDE;
+  const int Mc = batch * HC * WC;  // rows of this class
 
-  __shared__ bf16raw Ad[BM][BK + PAD];    // dY gather: [m2][kg_local]
+  __shared__ bf16raw Ad[BM][BK + PAD];    // dY gather: [row][co_local]
   __shared__ bf16raw Bd[CI][BK + PAD];    // W^T image: [ci][co_local]
 
   const int tid = threadIdx.x;
@@ -750,17 +625,18 @@ __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
     for (int ni = 0; ni < NFRAG; ++ni)
       acc[mi][ni] = {0.f, 0.f, 0.f, 0.f};
 
-  // per-thread A staging: row = tid>>1, kg-half = (tid&1)*16
+  // per-thread A staging: row = tid>>1, co-half = (tid&1)*16; the row is
+  // pixel (hc*STRIDE + ph, wc*STRIDE + pw) of image n_idx
   const int a_row = tid >> 1;
   const int a_k0 = (tid & 1) * 16;
-  const int m2 = row0 + a_row;
-  const int n_idx = m2 / (HI * WI);
-  const int rem = m2 - n_idx * (HI * WI);
-  const int hi = rem / WI;
-  const int wi = rem - hi * WI;
+  const int mc = row0 + a_row;
+  const int n_idx = mc / (HC * WC);
+  const int rem = mc - n_idx * (HC * WC);
+  const int hc = rem / WC;
+  const int wc = rem - hc * WC;
 
-  // software-pipelined: next tap-chunk's globals prefetch into registers
-  // during this chunk's MFMA (see wgrad note)
+  // software-pipelined: next step's globals prefetch into registers
+  // during this step's MFMA (see wgrad note)
   uint4 rda0, rda1;
   bf16raw rbw[8];
   // 4 (CI=32) or 8 (CI=64)
@@ -768,24 +644,14 @@ __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
   const int b_col = tid % BK;
   const int b_ci0 = (tid / BK) * CI_PER_T;
 
-  auto load_chunk = [&](int kg0) {
-    const int tap = kg0 / CO;
-    const int co0 = kg0 - tap * CO;
-    const int kh = tap / KW;
-    const int kw = tap - kh * KW;
-    bool valid = (m2 < M2);
-    int ho = 0, wo = 0;
-    if (valid) {
-      const int hh = hi - kh;
-      const int ww = wi - kw;
-      valid = hh >= 0 && ww >= 0 && (hh % STRIDE) == 0 && (ww % STRIDE) == 0;
-      if (valid) {
-        ho = hh / STRIDE;
-        wo = ww / STRIDE;
-        valid = ho < HO && wo < WO;
-      }
-    }
-    if (valid) {
+  auto load_chunk = [&](int step) {
+    const int t = step / (CO / BK);  // live tap (i, j), row-major
+    const int co0 = (step - t * (CO / BK)) * BK;
+    const int i = t / TW;
+    const int j = t - i * TW;
+    const int ho = hc - i;
+    const int wo = wc - j;
+    if (mc < Mc && ho >= 0 && ho < HO && wo >= 0 && wo < WO) {
       const bf16raw* src =
           dy + ((long long)(n_idx * HO + ho) * WO + wo) * CO + co0 + a_k0;
       rda0 = *reinterpret_cast<const uint4*>(src);
@@ -794,6 +660,7 @@ __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
       rda0 = uint4{0, 0, 0, 0};
       rda1 = uint4{0, 0, 0, 0};
     }
+    const int tap = (ph + STRIDE * i) * KW + pw + STRIDE * j;
     const bf16raw* src = w + (long long)(co0 + b_col) * K + tap * CI + b_ci0;
 #pragma unroll
     for (int e = 0; e < CI_PER_T; ++e) rbw[e] = src[e];
@@ -806,152 +673,31 @@ __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
     for (int e = 0; e < CI_PER_T; ++e) Bd[b_ci0 + e][b_col] = rbw[e];
   };
 
+  // fully unrolled: every step's tap and co block fold to constants
   load_chunk(0);
-  for (int kg0 = 0; kg0 < Kg; kg0 += BK) {
+#pragma unroll
+  for (int step = 0; step < NSTEPS; ++step) {
     store_chunk();
     __syncthreads();
-    if (kg0 + BK < Kg) load_chunk(kg0 + BK);
-
-    for (int mi = 0; mi < 2; ++mi) {
-      const bf16x8 a_frag = *reinterpret_cast<const bf16x8*>(
-          &Ad[wave * 32 + mi * 16 + (lane & 15)][(lane >> 4) * 8]);
-      for (int ni = 0; ni < NFRAG; ++ni) {
-        const bf16x8 b_frag = *reinterpret_cast<const bf16x8*>(
-            &Bd[ni * 16 + (lane & 15)][(lane >> 4) * 8]);
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a_frag, b_frag, acc[mi][ni], 0, 0, 0);
-      }
-    }
+    if (step + 1 < NSTEPS) load_chunk(step + 1);
+    drla_mfma_step_kmajor<NFRAG>(Ad, Bd, wave, lane, acc);
     __syncthreads();
   }
 
   for (int mi = 0; mi < 2; ++mi) {
-    for (int ni = 0; ni < NFRAG; ++ni) {
-      const int ci = ni * 16 + (lane & 15);
-      for (int r = 0; r < 4; ++r) {
-        const int grow = row0 + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
-        if (grow < M2) {
-          dx[(long long)grow * CI + ci] = drla_f32_to_bf16(acc[mi][ni][r]);
+    for (int r = 0; r < 4; ++r) {
+      const int grow = row0 + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
+      if (grow < Mc) {
+        long long pix = grow;  // STRIDE == 1: the one class is the image
+        if constexpr (STRIDE > 1) {
+          const int gn = grow / (HC * WC);
+          const int grem = grow - gn * (HC * WC);
+          const int ghc = grem / WC;
+          pix = ((long long)gn * HI + ghc * STRIDE + ph) * WI +
+                (grem - ghc * WC) * STRIDE + pw;
         }
-      }
-    }
-  }
-}
-
-// stride-2 dgrad, parity-class decomposition: for fixed (hi%2, wi%2) only
-// taps with kh≡hi, kw≡wi (mod 2) can contribute, so 4 of the 16 taps are
-// live — the generic kernel burns 3/4 of its k-loop staging zeros. Blocks
-// are grouped by parity class (blockIdx.y) so the whole block walks just
-// the 4 live taps: 8 BK=32 iterations instead of 32.
-template <int CI, int CO, int KH, int KW, int HI, int WI, int HO, int WO>
-__device__ void conv_dgrad_s2_impl(const bf16raw* __restrict__ dy,
-                                   const bf16raw* __restrict__ w,
-                                   bf16raw* __restrict__ dx, int batch) {
-  constexpr int K = KH * KW * CI;
-  constexpr int BM = DRLA_CONV_BM;
-  constexpr int BK = 32;
-  constexpr int PAD = 8;
-  constexpr int NFRAG = CI / 16;
-  constexpr int H2 = HI / 2, W2 = WI / 2;   // per-class extent
-  const int ph = blockIdx.y >> 1, pw = blockIdx.y & 1;
-  const int Mc = batch * H2 * W2;           // rows in this class
-
-  __shared__ bf16raw Ad[BM][BK + PAD];
-  __shared__ bf16raw Bd[CI][BK + PAD];
-
-  const int tid = threadIdx.x;
-  const int wave = tid / 64;
-  const int lane = tid % 64;
-  const int row0 = blockIdx.x * BM;
-
-  f32x4 acc[2][NFRAG];
-  for (int mi = 0; mi < 2; ++mi)
-    for (int ni = 0; ni < NFRAG; ++ni)
-      acc[mi][ni] = {0.f, 0.f, 0.f, 0.f};
-
-  const int a_row = tid >> 1;
-  const int a_k0 = (tid & 1) * 16;
-  const int mc = row0 + a_row;
-  const int n_idx = mc / (H2 * W2);
-  const int rem = mc - n_idx * (H2 * W2);
-  const int hi = (rem / W2) * 2 + ph;
-  const int wi = (rem - (rem / W2) * W2) * 2 + pw;
-
-  uint4 rda0, rda1;
-  bf16raw rbw[8];
-  constexpr int CI_PER_T = (CI * BK) / DRLA_CONV_BLOCK;
-  const int b_col = tid % BK;
-  const int b_ci0 = (tid / BK) * CI_PER_T;
-  constexpr int NIT = 4 * (CO / BK);
-
-  auto load_chunk = [&](int it) {
-    const int t = it / (CO / BK);           // live tap 0..3
-    const int co0 = (it - t * (CO / BK)) * BK;
-    const int kh = ph + 2 * (t >> 1);
-    const int kw = pw + 2 * (t & 1);
-    bool valid = (mc < Mc);
-    int ho = 0, wo = 0;
-    if (valid) {
-      const int hh = hi - kh;
-      const int ww = wi - kw;
-      valid = hh >= 0 && ww >= 0;
-      if (valid) {
-        ho = hh >> 1;
-        wo = ww >> 1;
-        valid = ho < HO && wo < WO;
-      }
-    }
-    if (valid) {
-      const bf16raw* src =
-          dy + ((long long)(n_idx * HO + ho) * WO + wo) * CO + co0 + a_k0;
-      rda0 = *reinterpret_cast<const uint4*>(src);
-      rda1 = *reinterpret_cast<const uint4*>(src + 8);
-    } else {
-      rda0 = uint4{0, 0, 0, 0};
-      rda1 = uint4{0, 0, 0, 0};
-    }
-    const int tap = kh * KW + kw;
-    const bf16raw* src = w + (long long)(co0 + b_col) * K + tap * CI + b_ci0;
-#pragma unroll
-    for (int e = 0; e < CI_PER_T; ++e) rbw[e] = src[e];
-  };
-
-  auto store_chunk = [&]() {
-    *reinterpret_cast<uint4*>(&Ad[a_row][a_k0]) = rda0;
-    *reinterpret_cast<uint4*>(&Ad[a_row][a_k0 + 8]) = rda1;
-#pragma unroll
-    for (int e = 0; e < CI_PER_T; ++e) Bd[b_ci0 + e][b_col] = rbw[e];
-  };
-
-  load_chunk(0);
-  for (int it = 0; it < NIT; ++it) {
-    store_chunk();
-    __syncthreads();
-    if (it + 1 < NIT) load_chunk(it + 1);
-    for (int mi = 0; mi < 2; ++mi) {
-      const bf16x8 a_frag = *reinterpret_cast<const bf16x8*>(
-          &Ad[wave * 32 + mi * 16 + (lane & 15)][(lane >> 4) * 8]);
-      for (int ni = 0; ni < NFRAG; ++ni) {
-        const bf16x8 b_frag = *reinterpret_cast<const bf16x8*>(
-            &Bd[ni * 16 + (lane & 15)][(lane >> 4) * 8]);
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a_frag, b_frag, acc[mi][ni], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-
-  for (int mi = 0; mi < 2; ++mi) {
-    for (int ni = 0; ni < NFRAG; ++ni) {
-      const int ci = ni * 16 + (lane & 15);
-      for (int r = 0; r < 4; ++r) {
-        const int growc = row0 + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
-        if (growc < Mc) {
-          const int gn = growc / (H2 * W2);
-          const int grem = growc - gn * (H2 * W2);
-          const int ghi = (grem / W2) * 2 + ph;
-          const int gwi = (grem - (grem / W2) * W2) * 2 + pw;
-          dx[(((long long)gn * HI + ghi) * WI + gwi) * CI + ci] =
+        for (int ni = 0; ni < NFRAG; ++ni) {
+          dx[pix * CI + ni * 16 + (lane & 15)] =
               drla_f32_to_bf16(acc[mi][ni][r]);
         }
       }
@@ -961,10 +707,7 @@ __device__ void conv_dgrad_s2_impl(const bf16raw* __restrict__ dy,
 
 CONV_KERNEL drla_conv_dgrad_l2(
     const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch) {
-  constexpr DrlaConvLayer g = DRLA_CONV_LAYERS[2];
-  static_assert(g.stride == 2, "the parity-class dgrad is stride-2 only");
-  conv_dgrad_s2_impl<g.ci, g.co, g.kh, g.kw, g.hi, g.wi, g.ho, g.wo>(
-      dy, w, dx, batch);
+  conv_dgrad_impl<DRLA_CONV_GEOM(2)>(dy, w, dx, batch);
 }
 CONV_KERNEL drla_conv_dgrad_l3(
     const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch) {

@@ -31,26 +31,17 @@
 // the result the bias gradient sum_m dY[m][co] - same pass, same MFMAs.
 // Partials go to a persistent f32 scratch [K+1][CO] by atomicAdd;
 // drla_c3_wgrad_finalize casts it to bf16 [CO][K] + [CO] and re-zeroes it.
+//
+// CONV_KERNEL, the packed-bf16 helpers (drla_bf16x2_*) and the transposed
+// fragment read (drla_lds_tr_frag) come from conv_tile.h, shared with
+// conv.hip. The MFMA step of c3_gemm_impl stays written out here: its
+// operand roles are swapped and the weight fragments are held across both
+// row tiles, which drla_mfma_step_kmajor does not do.
 
 #include "drla_kernels.h"
-
-#define CONV_KERNEL \
-  extern "C" __global__ __launch_bounds__(DRLA_CONV_BLOCK) void
+#include "conv_tile.h"
 
 namespace {
-
-// max(x, 0) on two packed bf16: a set sign bit clears its half
-__device__ __forceinline__ unsigned int c3_relu2(unsigned int v) {
-  const unsigned int neg = (v >> 15) & 0x00010001u;
-  return v & ~(neg * 0xFFFFu);
-}
-
-__device__ __forceinline__ float c3_lo(unsigned int v) {
-  return __uint_as_float(v << 16);
-}
-__device__ __forceinline__ float c3_hi(unsigned int v) {
-  return __uint_as_float(v & 0xFFFF0000u);
-}
 
 // ---------------------------------------------------------------------------
 // forward / dgrad
@@ -178,10 +169,10 @@ __device__ void c3_gemm_impl(const bf16raw* __restrict__ in,    // [M][CIN]
         ra1 = uint4{u[2].x, u[2].y, u[3].x, u[3].y};
       }
       if (relu_in) {
-        ra0.x = c3_relu2(ra0.x); ra0.y = c3_relu2(ra0.y);
-        ra0.z = c3_relu2(ra0.z); ra0.w = c3_relu2(ra0.w);
-        ra1.x = c3_relu2(ra1.x); ra1.y = c3_relu2(ra1.y);
-        ra1.z = c3_relu2(ra1.z); ra1.w = c3_relu2(ra1.w);
+        ra0.x = drla_bf16x2_relu(ra0.x); ra0.y = drla_bf16x2_relu(ra0.y);
+        ra0.z = drla_bf16x2_relu(ra0.z); ra0.w = drla_bf16x2_relu(ra0.w);
+        ra1.x = drla_bf16x2_relu(ra1.x); ra1.y = drla_bf16x2_relu(ra1.y);
+        ra1.z = drla_bf16x2_relu(ra1.z); ra1.w = drla_bf16x2_relu(ra1.w);
       }
     };
 
@@ -226,17 +217,17 @@ __device__ void c3_gemm_impl(const bf16raw* __restrict__ in,    // [M][CIN]
           float v3 = acc[mi][ni][3] + BiasBuf[c0 + 3];
           if (mask) {
             const uint2 mv = *reinterpret_cast<const uint2*>(mask + off);
-            v0 *= (c3_lo(mv.x) > 0.0f) ? 1.0f : 0.0f;
-            v1 *= (c3_hi(mv.x) > 0.0f) ? 1.0f : 0.0f;
-            v2 *= (c3_lo(mv.y) > 0.0f) ? 1.0f : 0.0f;
-            v3 *= (c3_hi(mv.y) > 0.0f) ? 1.0f : 0.0f;
+            v0 *= (drla_bf16x2_lo(mv.x) > 0.0f) ? 1.0f : 0.0f;
+            v1 *= (drla_bf16x2_hi(mv.x) > 0.0f) ? 1.0f : 0.0f;
+            v2 *= (drla_bf16x2_lo(mv.y) > 0.0f) ? 1.0f : 0.0f;
+            v3 *= (drla_bf16x2_hi(mv.y) > 0.0f) ? 1.0f : 0.0f;
           }
           if (res) {
             const uint2 rv = *reinterpret_cast<const uint2*>(res + off);
-            v0 += c3_lo(rv.x);
-            v1 += c3_hi(rv.x);
-            v2 += c3_lo(rv.y);
-            v3 += c3_hi(rv.y);
+            v0 += drla_bf16x2_lo(rv.x);
+            v1 += drla_bf16x2_hi(rv.x);
+            v2 += drla_bf16x2_lo(rv.y);
+            v3 += drla_bf16x2_hi(rv.y);
           }
           uint2 o;
           o.x = drla_f32x2_to_bf16x2(v0, v1);
@@ -251,19 +242,6 @@ __device__ void c3_gemm_impl(const bf16raw* __restrict__ in,    // [M][CIN]
 // ---------------------------------------------------------------------------
 // wgrad + bias gradient
 // ---------------------------------------------------------------------------
-
-// one 16x16x32 operand from a row-major LDS tile of `pitch` bytes per row:
-// two ds_read_b64_tr_b16 (rows 8g..8g+3 at p, 8g+4..8g+7 four rows down).
-// The gather crosses lanes: callers keep EXEC full around it.
-__device__ __forceinline__ bf16x8 c3_lds_tr_frag(const unsigned char* p,
-                                                 int pitch) {
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4* lds_ptr;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p);
-  const s16x4 hi =
-      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(p + 4 * pitch));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 template <int CI, int CO, int HW>
 __device__ void c3_wgrad_impl(const bf16raw* __restrict__ in,   // [M][CI]
@@ -347,8 +325,8 @@ __device__ void c3_wgrad_impl(const bf16raw* __restrict__ in,   // [M][CI]
         }
       }
       if (relu_in) {
-        v.x = c3_relu2(v.x); v.y = c3_relu2(v.y);
-        v.z = c3_relu2(v.z); v.w = c3_relu2(v.w);
+        v.x = drla_bf16x2_relu(v.x); v.y = drla_bf16x2_relu(v.y);
+        v.z = drla_bf16x2_relu(v.z); v.w = drla_bf16x2_relu(v.w);
       }
       unsigned char* dst = &Am[row * APITCH + (tap * CI + c0) * 2];
       if constexpr (EL == 8) {
@@ -375,14 +353,14 @@ __device__ void c3_wgrad_impl(const bf16raw* __restrict__ in,   // [M][CI]
       bf16x8 yf[NFRAG];
 #pragma unroll
       for (int ni = 0; ni < NFRAG; ++ni) {
-        yf[ni] = c3_lds_tr_frag(
+        yf[ni] = drla_lds_tr_frag(
             &Bm[(ks * 32 + tr_row) * BPITCH + ni * 32 + tr_col], BPITCH);
       }
 #pragma unroll
       for (int ti = 0; ti < TPW; ++ti) {
         const int t = wave + 4 * ti;  // wave-uniform
         if (t < KT) {
-          const bf16x8 af = c3_lds_tr_frag(
+          const bf16x8 af = drla_lds_tr_frag(
               &Am[(ks * 32 + tr_row) * APITCH + t * 32 + tr_col], APITCH);
 #pragma unroll
           for (int ni = 0; ni < NFRAG; ++ni) {
