@@ -9,8 +9,10 @@ Atari stack — the config that stresses the gradient all-reduce.
 
 On the GPU with bf16 weights all 15 convolutions, the pre-activation ReLUs
 and the residual adds run on the hand-written MFMA 3x3 kernels
-(ops/hip/conv3x3.hip through ops/resnet_op.py), forward and backward;
-max-pool, the final ReLU and fc stay torch ops on channels_last views.
+(ops/hip/conv3x3.hip through ops/resnet_op.py), forward and backward, and
+the three max-pools on ops/hip/maxpool.hip (ops/pool_op.py;
+DRLA_RESNET_POOL=0 keeps F.max_pool2d there); the final ReLU and fc stay
+torch ops.
 Everywhere else (CPU actors, fp32 weights, DRLA_RESNET_CONV=0) the torso
 runs channels_last nn.Conv2d, which is also the reference of the custom
 path. The conv weights are channels_last from construction, so the custom

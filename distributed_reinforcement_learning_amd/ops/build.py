@@ -32,6 +32,7 @@ SOURCES = [
     "optim.hip",
     "conv.hip",
     "conv3x3.hip",
+    "maxpool.hip",
     "per_tree.hip",
     "dqn_loss.hip",
     "a2c_loss.hip",

@@ -1562,6 +1562,80 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
   adam_step_t(p, g, m, v, clip, lr_buf, beta1, beta2, eps);
 }
 
+// ---- 3x3 / stride 2 / padding 1 max-pool (maxpool.hip) ---------------------
+// t is [N, h, w, C] dense with C = 16 or 32. The kernels count rows (N*h) in
+// int and elements in 64 bits, and stage whole rows in LDS: both are checked.
+// a lane moves 8 channels at once: 16 bytes of bf16, 8 bytes of tap
+void check_pool_aligned(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) %
+                      (8 * t.element_size()) == 0,
+              name, " must start at a multiple of ", 8 * t.element_size(),
+              " bytes");
+}
+void check_pool_tensor(const torch::Tensor& t, int64_t h, int64_t w,
+                       torch::ScalarType dtype, const char* name) {
+  check_gpu_contig(t, name);
+  TORCH_CHECK(t.scalar_type() == dtype, name, " has the wrong dtype");
+  TORCH_CHECK(t.dim() == 4 && t.size(1) == h && t.size(2) == w && h >= 1 &&
+                  w >= 1,
+              name, " must be [N, ", h, ", ", w, ", C]");
+  TORCH_CHECK(t.size(3) == 16 || t.size(3) == 32,
+              "the max-pool kernels take 16 or 32 channels");
+  TORCH_CHECK(t.size(0) * h < (int64_t(1) << 30), name,
+              ": too many rows for the max-pool kernels");
+  TORCH_CHECK(w * t.size(3) <= DRLA_POOL_MAX_ROW_ELEMS, name,
+              ": row too wide for the max-pool kernels");
+  check_pool_aligned(t, name);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> maxpool3s2_fwd(
+    const torch::Tensor& x, bool want_tap) {
+  TORCH_CHECK(x.dim() == 4, "x must be [N, H, W, C]");
+  const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  check_pool_tensor(x, x.size(1), x.size(2), torch::kBFloat16, "x");
+  const int HO = drla_pool_out(H), WO = drla_pool_out(W);
+  auto y = torch::empty({N, HO, WO, C}, x.options());
+  torch::Tensor tap;
+  if (want_tap) {
+    tap = torch::empty({N, HO, WO, C}, x.options().dtype(torch::kUInt8));
+  }
+  if (N == 0) return {y, tap};
+  const int rows = drla_pool_fwd_rows(W, C);
+  hipLaunchKernelGGL(
+      C == 16 ? drla_maxpool3s2_fwd_c16 : drla_maxpool3s2_fwd_c32,
+      dim3((N * HO + rows - 1) / rows), dim3(DRLA_BLOCK),
+      drla_pool_fwd_lds_bytes(W, C, rows), cur_stream(), BF16P(x), BF16PM(y),
+      want_tap ? tap.data_ptr<uint8_t>() : nullptr, N, H, W, HO, WO, rows);
+  return {y, tap};
+}
+
+torch::Tensor maxpool3s2_bwd(const torch::Tensor& dy, const torch::Tensor& tap,
+                             int64_t H, int64_t W,
+                             const c10::optional<torch::Tensor>& addend) {
+  TORCH_CHECK(dy.dim() == 4 && H >= 1 && W >= 1 && H < (int64_t(1) << 30) &&
+                  dy.size(0) * H < (int64_t(1) << 30) &&
+                  W * dy.size(3) <= DRLA_POOL_MAX_ROW_ELEMS,
+              "dy must be [N, HO, WO, C] and H, W the size of the pooled "
+              "image, within the row limits of the max-pool kernels");
+  const int N = dy.size(0), C = dy.size(3);
+  const int HO = drla_pool_out(H), WO = drla_pool_out(W);
+  check_pool_tensor(dy, HO, WO, torch::kBFloat16, "dy");
+  check_pool_tensor(tap, HO, WO, torch::kUInt8, "tap");
+  TORCH_CHECK(tap.sizes() == dy.sizes(), "tap must be shaped like dy");
+  auto dx = torch::empty({N, H, W, C}, dy.options());
+  const bf16raw* addp = conv3_opt(addend, dx, "addend");
+  if (addp) check_pool_aligned(*addend, "addend");
+  if (N == 0) return dx;
+  const int pairs = drla_pool_bwd_pairs(WO, C);
+  hipLaunchKernelGGL(
+      C == 16 ? drla_maxpool3s2_bwd_c16 : drla_maxpool3s2_bwd_c32,
+      dim3((N * HO + pairs - 1) / pairs), dim3(DRLA_BLOCK),
+      drla_pool_bwd_lds_bytes(WO, C, pairs), cur_stream(), BF16P(dy),
+      static_cast<const unsigned char*>(tap.data_ptr<uint8_t>()), addp,
+      BF16PM(dx), N, (int)H, (int)W, HO, WO, pairs);
+  return dx;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1604,6 +1678,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mask_src") = py::none(), py::arg("addend") = py::none());
   m.def("relu_mask_bwd", &relu_mask_bwd,
         "fused-ReLU backward mask + bias gradient");
+  // underscore: reached through ops/pool_op.py only
+  m.def("_maxpool3s2_fwd", &maxpool3s2_fwd,
+        "3x3/2 max-pool, NHWC bf16 -> (y, one-byte tap or None)",
+        py::arg("x"), py::arg("want_tap"));
+  m.def("_maxpool3s2_bwd", &maxpool3s2_bwd,
+        "3x3/2 max-pool backward: gather of dy by tap (+ addend)",
+        py::arg("dy"), py::arg("tap"), py::arg("H"), py::arg("W"),
+        py::arg("addend") = py::none());
   m.def("dqn_loss_fwd", &dqn_loss_fwd,
         "fused double-DQN target + IS-weighted TD loss (K8)");
   m.def("dqn_loss_bwd", &dqn_loss_bwd, "closed-form K8 backward");

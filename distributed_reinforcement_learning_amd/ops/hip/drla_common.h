@@ -60,6 +60,34 @@ constexpr DrlaConv3Layer DRLA_CONV3_LAYERS[DRLA_CONV3_COUNT] = {
 // wgrad scratch: [9*ci + 1][co] f32, the last row is the bias gradient
 constexpr int DRLA_CONV3_SCRATCH_ELEMS = (9 * 32 + 1) * 32;
 
+// 3x3 / stride 2 / padding 1 max-pool (maxpool.hip), NHWC bf16, C = 16 or 32.
+// A forward block owns `rows` output rows and stages their 2*rows + 1 input
+// rows in dynamic LDS; a backward block owns `pairs` output rows (= 2*pairs
+// input rows) and stages pairs + 1 rows of dY (2 B) and tap (1 B). Both tile
+// heights are chosen by the launcher from the row size and passed in.
+#define DRLA_POOL_MAX_ROWS 8             // tile height cap, both directions
+#define DRLA_POOL_LDS_TARGET (32 * 1024)  // dynamic LDS a block aims for
+#define DRLA_POOL_MAX_ROW_ELEMS 8192     // W * C; 3 input rows stay < 64 KB
+constexpr int drla_pool_out(int in) { return (in - 1) / 2 + 1; }
+constexpr int drla_pool_clamp_rows(int r) {
+  return r < 1 ? 1 : (r > DRLA_POOL_MAX_ROWS ? DRLA_POOL_MAX_ROWS : r);
+}
+constexpr int drla_pool_fwd_rows(int w, int c) {
+  return drla_pool_clamp_rows((DRLA_POOL_LDS_TARGET / (w * c * 2) - 1) / 2);
+}
+constexpr int drla_pool_fwd_lds_bytes(int w, int c, int rows) {
+  return (2 * rows + 1) * w * c * 2;
+}
+constexpr int drla_pool_bwd_pairs(int wo, int c) {
+  return drla_pool_clamp_rows(DRLA_POOL_LDS_TARGET / (wo * c * 3) - 1);
+}
+constexpr int drla_pool_bwd_lds_bytes(int wo, int c, int pairs) {
+  return (pairs + 1) * wo * c * 3;
+}
+static_assert(drla_pool_fwd_lds_bytes(DRLA_POOL_MAX_ROW_ELEMS, 1, 1) <=
+                  64 * 1024,
+              "the widest row still fits one forward tile");
+
 // fused V-trace loss: T sizes the LDS scan buffers, A is the softmax width
 #define VT_MAX_T 128
 #define VT_MAX_A 64

@@ -159,6 +159,20 @@ DRLA_KERNEL drla_c3_wgrad_32_32_11(const bf16raw*, const bf16raw*, float*,
     int, int);
 DRLA_KERNEL drla_c3_wgrad_finalize(float*, bf16raw*, bf16raw*, int, int);
 
+// ---- maxpool.hip (3x3 / stride 2 / padding 1, NHWC bf16) ------------------
+// fwd: x, y, tap / null, N, H, W, HO, WO, output rows per block
+DRLA_KERNEL drla_maxpool3s2_fwd_c16(const bf16raw*, bf16raw*, unsigned char*,
+                                    int, int, int, int, int, int);
+DRLA_KERNEL drla_maxpool3s2_fwd_c32(const bf16raw*, bf16raw*, unsigned char*,
+                                    int, int, int, int, int, int);
+// bwd: dy, tap, addend / null, dx, N, H, W, HO, WO, output rows per block
+DRLA_KERNEL drla_maxpool3s2_bwd_c16(const bf16raw*, const unsigned char*,
+                                    const bf16raw*, bf16raw*, int, int, int,
+                                    int, int, int);
+DRLA_KERNEL drla_maxpool3s2_bwd_c32(const bf16raw*, const unsigned char*,
+                                    const bf16raw*, bf16raw*, int, int, int,
+                                    int, int, int);
+
 // ---- per_tree.hip ---------------------------------------------------------
 DRLA_KERNEL drla_per_update(float*, const long long*, const float*, int,
                             long long);

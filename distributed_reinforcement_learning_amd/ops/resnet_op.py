@@ -10,6 +10,8 @@ x + c2(relu(c1(relu(x)))) is two forward launches (input ReLU fused into the
 A-tile staging, skip add fused into the second epilogue) and four backward
 MFMA launches plus the two wgrad finalizes; the ReLU masks and the skip
 gradient ride in the dgrad epilogues, so no elementwise torch op runs.
+The 3x3/2 max-pool between a section conv and its blocks is ops/pool_op.py
+(ops/hip/maxpool.hip); DRLA_RESNET_POOL=0 keeps the library pool there.
 Weights are consumed as the channels_last flat view [CO][9*CI], built
 in-graph so the gradients flow back to the nn.Conv2d parameters.
 """
@@ -22,6 +24,9 @@ import torch
 import torch.nn.functional as F
 
 from distributed_reinforcement_learning_amd import ops as _ops
+from distributed_reinforcement_learning_amd.ops.pool_op import (
+    library_pool3x3s2, max_pool3x3s2,
+)
 
 # (section conv layer id, residual block layer id) per section
 SECTION_LAYERS = ((4, 5), (6, 7), (7, 8))
@@ -96,16 +101,16 @@ def res_block(x_nhwc: torch.Tensor, block, layer: int) -> torch.Tensor:
 
 
 def resnet_torso(torso, x_nhwc: torch.Tensor) -> torch.Tensor:
-    """bf16 [N,84,84,4] -> the torso's [N,256] features. Convs, input ReLUs
-    and skip adds run on the custom kernels; max-pool, the last ReLU and fc
-    stay torch ops on channels_last views (the NCHW view of an NHWC tensor
-    IS channels_last, and the pool keeps that format, so neither permute
-    copies)."""
+    """bf16 [N,84,84,4] -> the torso's [N,256] features. Convs, input ReLUs,
+    skip adds and the max-pools run on the custom kernels; the last ReLU and
+    fc stay torch ops. DRLA_RESNET_POOL=0 (read at call time: the A/B
+    switch) runs the library max-pool instead."""
+    pool = (library_pool3x3s2 if os.environ.get("DRLA_RESNET_POOL") == "0"
+            else max_pool3x3s2)
     x = x_nhwc
     for sec, (lc, lr) in zip(torso.sections, SECTION_LAYERS):
         x = conv3x3(x, sec.conv, lc)
-        x = F.max_pool2d(x.permute(0, 3, 1, 2), 3, stride=2, padding=1)
-        x = x.permute(0, 2, 3, 1)
+        x = pool(x)
         x = res_block(x, sec.r1, lr)
         x = res_block(x, sec.r2, lr)
     x = F.relu(x)
