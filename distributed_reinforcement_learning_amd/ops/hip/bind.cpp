@@ -435,11 +435,64 @@ std::tuple<torch::Tensor, torch::Tensor> conv3_wgrad(int layer,
   return {dw, dbias};
 }
 
+// persistent zero-between-calls f32 [K][CO] wgrad scratch of a layer 0..3
+// (the finalize re-zeroes it as it reads)
+static torch::Tensor& wgrad_scratch_buf(int layer) {
+  static torch::Tensor bufs[4];
+  return bufs[layer];
+}
+
+// one drla_wgrad_finalize launch, blockIdx.y = position in `layers`: scratch
+// -> bf16 dW [CO][K], bias-grad slot set -> bf16 dbias [CO], both re-zeroed
+static std::vector<std::tuple<torch::Tensor, torch::Tensor>>
+launch_wgrad_finalize(const std::vector<int64_t>& layers) {
+  TORCH_CHECK(!layers.empty() &&
+                  layers.size() <= (size_t)DRLA_FINALIZE_MAX_JOBS,
+              "finalize wants 1..", DRLA_FINALIZE_MAX_JOBS, " layers");
+  DrlaWgradFinalizeJobs jobs = {};
+  std::vector<std::tuple<torch::Tensor, torch::Tensor>> out;
+  long long max_elems = 0;
+  for (size_t j = 0; j < layers.size(); ++j) {
+    const int layer = (int)layers[j];
+    const auto& cfg = conv_layer(layer);
+    for (size_t i = 0; i < j; ++i) {
+      TORCH_CHECK(layers[i] != layers[j], "layer listed twice");
+    }
+    auto& scratch = wgrad_scratch_buf(layer);
+    TORCH_CHECK(scratch.defined(),
+                "no conv_wgrad of layer ", layer, " has run yet");
+    const int K = cfg.kh * cfg.kw * cfg.ci;
+    auto bf16 = scratch.options().dtype(torch::kBFloat16);
+    auto dw = torch::empty({cfg.co, K}, bf16);
+    auto dbias = torch::empty({cfg.co}, bf16);
+    jobs.scratch[j] = scratch.data_ptr<float>();
+    jobs.dw[j] = BF16PM(dw);
+    jobs.dbias_slots[j] = dbias_slot_buf(scratch, layer).data_ptr<float>();
+    jobs.dbias[j] = BF16PM(dbias);
+    jobs.K[j] = K;
+    jobs.CO[j] = cfg.co;
+    max_elems = std::max(max_elems, (long long)K * cfg.co);
+    out.emplace_back(dw, dbias);
+  }
+  hipLaunchKernelGGL(drla_wgrad_finalize,
+                     dim3(drla_grid(max_elems), (unsigned)layers.size()),
+                     dim3(DRLA_BLOCK), 0, cur_stream(), jobs);
+  return out;
+}
+
+// finalize = false launches only the wgrad kernel into the layer's persistent
+// scratch and returns undefined tensors: the caller MUST then run
+// _conv_wgrad_finalize_all with this layer listed before any other conv_wgrad
+// of the layer (the scratch and the slot set have to be zero again)
 std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
                                                     torch::Tensor in,
                                                     torch::Tensor dy,
-                                                    bool relu_in) {
-  if (is_conv3(layer)) return conv3_wgrad(layer, in, dy, relu_in);
+                                                    bool relu_in,
+                                                    bool finalize) {
+  if (is_conv3(layer)) {
+    TORCH_CHECK(finalize, "the 3x3 layers always finalize");
+    return conv3_wgrad(layer, in, dy, relu_in);
+  }
   TORCH_CHECK(!relu_in, "relu_in is a 3x3-layer option");
   check_gpu_contig(in, "in");
   check_gpu_contig(dy, "dy");
@@ -447,13 +500,11 @@ std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
   const int batch = in.size(0);
   const int K = cfg.kh * cfg.kw * cfg.ci;
   const int split = conv_wgrad_split(layer);
-  // persistent zero-between-calls scratch (finalize re-zeroes on read)
-  static torch::Tensor scratch_cache[4];
-  if (!scratch_cache[layer].defined()) {
-    scratch_cache[layer] =
-        torch::zeros({K, cfg.co}, dy.options().dtype(torch::kFloat));
+  auto& scratch = wgrad_scratch_buf(layer);
+  if (!scratch.defined()) {
+    scratch = torch::zeros({K, cfg.co}, dy.options().dtype(torch::kFloat));
   }
-  auto scratch = scratch_cache[layer];
+  dbias_slot_buf(dy, layer);  // allocated (zero) before any finalize
   const dim3 grid((K + DRLA_CONV_WGRAD_BK - 1) / DRLA_CONV_WGRAD_BK, split);
   if (layer <= 1) {
     hipLaunchKernelGGL(kConvWgradU8[layer], grid, dim3(DRLA_CONV_BLOCK), 0,
@@ -464,37 +515,66 @@ std::tuple<torch::Tensor, torch::Tensor> conv_wgrad(int layer,
                        dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(in),
                        BF16P(dy), scratch.data_ptr<float>(), batch);
   }
-  auto dw = torch::empty({cfg.co, K}, dy.options().dtype(torch::kBFloat16));
-  auto dbias = torch::empty({cfg.co}, dy.options().dtype(torch::kBFloat16));
-  auto& slots = dbias_slot_buf(dy, layer);
-  hipLaunchKernelGGL(drla_wgrad_finalize,
-                     dim3(drla_grid((long long)K * cfg.co)),
-                     dim3(DRLA_BLOCK), 0, cur_stream(),
-                     scratch.data_ptr<float>(), BF16PM(dw), K, cfg.co,
-                     slots.data_ptr<float>(), BF16PM(dbias));
-  return {dw, dbias};
+  if (!finalize) return {torch::Tensor(), torch::Tensor()};
+  return launch_wgrad_finalize({layer})[0];
 }
 
+// the (dw, dbias) pairs of any subset of layers 0..3 from ONE finalize
+// launch; every listed layer's scratch and slot set is zero afterwards and
+// no other layer's is touched
+std::vector<std::tuple<torch::Tensor, torch::Tensor>> conv_wgrad_finalize_all(
+    std::vector<int64_t> layers) {
+  return launch_wgrad_finalize(layers);
+}
+
+// mask_src + slot (layers 2/3): dx = dgrad * (mask_src > 0), mask_src the
+// output of the layer below, and that layer's bias-grad partials go into slot
+// set `slot` (its layer id: 0 or 1 under layer 2, 2 under layer 3) for its
+// wgrad finalize to drain
 torch::Tensor conv_dgrad(int layer, torch::Tensor dy, torch::Tensor w,
                          c10::optional<torch::Tensor> mask_src,
-                         c10::optional<torch::Tensor> addend) {
-  if (is_conv3(layer)) return conv3_dgrad(layer, dy, w, mask_src, addend);
-  TORCH_CHECK(!mask_src.has_value() && !addend.has_value(),
-              "mask_src/addend are 3x3-layer options");
+                         c10::optional<torch::Tensor> addend, int64_t slot) {
+  if (is_conv3(layer)) {
+    TORCH_CHECK(slot < 0, "the 3x3 layers take no slot");
+    return conv3_dgrad(layer, dy, w, mask_src, addend);
+  }
+  TORCH_CHECK(!addend.has_value(), "addend is a 3x3-layer option");
   check_gpu_contig(dy, "dy");
   check_gpu_contig(w, "w");
   TORCH_CHECK(layer == 2 || layer == 3, "dgrad only for l2/l3");
   const auto& cfg = conv_layer(layer);
   const int batch = dy.size(0);
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 && dy.dim() == 4 &&
+                  dy.size(1) == cfg.ho && dy.size(2) == cfg.wo &&
+                  dy.size(3) == cfg.co,
+              "dy must be bf16 [N, ", cfg.ho, ", ", cfg.wo, ", ", cfg.co, "]");
+  TORCH_CHECK(batch >= 1 &&
+                  (int64_t)batch * cfg.hi * cfg.wi < (int64_t(1) << 30),
+              "batch out of range for the conv kernels");
   auto dx = torch::empty({batch, cfg.hi, cfg.wi, cfg.ci},
                          dy.options().dtype(torch::kBFloat16));
+  const bf16raw* maskp = nullptr;
+  float* slotsp = nullptr;
+  if (mask_src.has_value()) {
+    check_gpu_contig(*mask_src, "mask_src");
+    TORCH_CHECK(mask_src->scalar_type() == torch::kBFloat16 &&
+                    mask_src->sizes() == dx.sizes(),
+                "mask_src must be bf16 and shaped like dx");
+    TORCH_CHECK(layer == 2 ? (slot == 0 || slot == 1) : slot == 2,
+                "slot names the layer below: 0 or 1 under layer 2, 2 under "
+                "layer 3");
+    maskp = BF16P(*mask_src);
+    slotsp = dbias_slot_buf(dy, slot).data_ptr<float>();
+  } else {
+    TORCH_CHECK(slot < 0, "slot goes with mask_src");
+  }
   // blockIdx.y = the (hi % s, wi % s) class, batch * (hi/s) * (wi/s) rows each
   const int s = cfg.stride;
   hipLaunchKernelGGL(
       kConvDgrad[layer - 2],
       dim3(conv_m_tiles(batch * (cfg.hi / s) * (cfg.wi / s)), s * s),
       dim3(DRLA_CONV_BLOCK), 0, cur_stream(), BF16P(dy), BF16P(w), BF16PM(dx),
-      batch);
+      batch, maskp, slotsp);
   return dx;
 }
 
@@ -1670,12 +1750,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_wgrad", &conv_wgrad,
         "MFMA conv weight + bias gradient (K1 bwd; layers 4..8: 3x3 family)",
         py::arg("layer"), py::arg("x"), py::arg("dy"),
-        py::arg("relu_in") = false);
+        py::arg("relu_in") = false, py::arg("finalize") = true);
+  // underscore: the public names are a frozen set (tests/test_ops_build.py);
+  // reached through ops/conv_op.py
+  m.def("_conv_wgrad_finalize_all", &conv_wgrad_finalize_all,
+        "one finalize launch for conv_wgrad(finalize=False) of layers 0..3: "
+        "[(dw, dbias)] in the order listed",
+        py::arg("layers"));
   m.def("_conv_wgrad_split", &conv_wgrad_split,
         "M-split of the conv wgrad grid for a layer");
   m.def("conv_dgrad", &conv_dgrad, "MFMA conv data gradient (K1 bwd)",
         py::arg("layer"), py::arg("dy"), py::arg("w"),
-        py::arg("mask_src") = py::none(), py::arg("addend") = py::none());
+        py::arg("mask_src") = py::none(), py::arg("addend") = py::none(),
+        py::arg("slot") = -1);
   m.def("relu_mask_bwd", &relu_mask_bwd,
         "fused-ReLU backward mask + bias gradient");
   // underscore: reached through ops/pool_op.py only

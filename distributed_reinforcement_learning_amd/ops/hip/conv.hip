@@ -336,13 +336,18 @@ extern "C" __global__ void drla_relu_mask_bwd(
 // cast + transpose the f32 [K][CO] wgrad scratch into bf16 [CO][K]
 // (the channels_last weight-grad layout), re-zeroing the persistent
 // scratch as it reads (zero-between-calls invariant, no fill kernel).
-extern "C" __global__ void drla_wgrad_finalize(
-    float* __restrict__ scratch, bf16raw* __restrict__ dw, int K,
-    int CO, float* __restrict__ dbias_slots,
-    bf16raw* __restrict__ dbias) {
-  // bias-grad epilogue: 16-way slot sum from relu_mask_bwd, bf16 out,
-  // slots re-zeroed (persistent zero-between-calls buffer)
-  if (dbias_slots && blockIdx.x == 0 && (int)threadIdx.x < CO) {
+// One job (layer) per blockIdx.y: the conv stack's backward finalizes its
+// three wgrads in one launch.
+extern "C" __global__ void drla_wgrad_finalize(DrlaWgradFinalizeJobs jobs) {
+  float* __restrict__ scratch = jobs.scratch[blockIdx.y];
+  bf16raw* __restrict__ dw = jobs.dw[blockIdx.y];
+  float* __restrict__ dbias_slots = jobs.dbias_slots[blockIdx.y];
+  bf16raw* __restrict__ dbias = jobs.dbias[blockIdx.y];
+  const int K = jobs.K[blockIdx.y];
+  const int CO = jobs.CO[blockIdx.y];
+  // bias-grad epilogue: 16-way slot sum from relu_mask_bwd or the masked
+  // dgrad, bf16 out, slots re-zeroed (persistent zero-between-calls buffer)
+  if (blockIdx.x == 0 && (int)threadIdx.x < CO) {
     float s = 0.0f;
     for (int t = 0; t < DRLA_DBIAS_SLOTS; ++t) {
       s += dbias_slots[t * DRLA_DBIAS_STRIDE + threadIdx.x];
@@ -596,7 +601,14 @@ template <int CI, int CO, int KH, int KW, int STRIDE, int HI, int WI, int HO,
 __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
                                 const bf16raw* __restrict__ w,   // [CO][K]
                                 bf16raw* __restrict__ dx,  // [N][HI][WI][CI]
-                                int batch) {
+                                int batch,
+                                const bf16raw* __restrict__ mask_src,
+                                float* __restrict__ dbias_slots) {
+  // mask_src (both or neither with dbias_slots): the output Y of the layer
+  // below, shaped like dx. The epilogue then is that layer's ReLU backward:
+  // dx = bf16(acc) where Y > 0 and 0 elsewhere, bit for bit what
+  // drla_relu_mask_bwd makes of the unmasked dx, and the column sums of the
+  // masked values go into the layer's bias-grad slot set.
   constexpr int K = KH * KW * CI;
   constexpr int BM = DRLA_CONV_BM;
   constexpr int BK = 32;   // one tap x 32 co per step
@@ -684,32 +696,98 @@ __device__ void conv_dgrad_impl(const bf16raw* __restrict__ dy,  // [M][CO]
     __syncthreads();
   }
 
+  // image pixel of row grow of this class
+  auto pix_of = [&](int grow) -> long long {
+    if constexpr (STRIDE > 1) {
+      const int gn = grow / (HC * WC);
+      const int grem = grow - gn * (HC * WC);
+      const int ghc = grem / WC;
+      return ((long long)gn * HI + ghc * STRIDE + ph) * WI +
+             (grem - ghc * WC) * STRIDE + pw;
+    } else {
+      return grow;  // the one class is the image
+    }
+  };
+
+  // masked path: every mask value of the lane is requested before the first
+  // is used (one memory latency, not one per row: loading inside the store
+  // loop cost 7-10 us per kernel). No row branch here: rows past Mc read
+  // the class's last row, which exists, and are never stored or summed.
+  bf16raw mv[2][4][NFRAG];
+  if (mask_src) {
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int grow = row0 + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
+        const long long base = pix_of(min(grow, Mc - 1)) * CI;
+#pragma unroll
+        for (int ni = 0; ni < NFRAG; ++ni) {
+          mv[mi][r][ni] = mask_src[base + ni * 16 + (lane & 15)];
+        }
+      }
+    }
+    // left to itself the scheduler sinks each load to its use and waits for
+    // it there, to save registers: 16-32 latencies in a row
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // column sums of the stored values, rows < Mc only (masked path)
+  float colsum[NFRAG];
+  for (int ni = 0; ni < NFRAG; ++ni) colsum[ni] = 0.0f;
+
+#pragma unroll
   for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int grow = row0 + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
       if (grow < Mc) {
-        long long pix = grow;  // STRIDE == 1: the one class is the image
-        if constexpr (STRIDE > 1) {
-          const int gn = grow / (HC * WC);
-          const int grem = grow - gn * (HC * WC);
-          const int ghc = grem / WC;
-          pix = ((long long)gn * HI + ghc * STRIDE + ph) * WI +
-                (grem - ghc * WC) * STRIDE + pw;
-        }
+        const long long pix = pix_of(grow);
+#pragma unroll
         for (int ni = 0; ni < NFRAG; ++ni) {
-          dx[pix * CI + ni * 16 + (lane & 15)] =
-              drla_f32_to_bf16(acc[mi][ni][r]);
+          bf16raw v = drla_f32_to_bf16(acc[mi][ni][r]);
+          if (mask_src) {
+            // the bf16 view of Y: +0, -0 and negatives all clear
+            if (!(drla_bf16_to_f32(mv[mi][r][ni]) > 0.0f)) v = 0;
+            colsum[ni] += drla_bf16_to_f32(v);
+          }
+          dx[pix * CI + ni * 16 + (lane & 15)] = v;
         }
       }
+    }
+  }
+
+  // bias-grad partials (block-uniform branch): sum the four lane>>4 row
+  // groups of a wave, then the four waves through LDS (the A tile is free
+  // after the loop's last barrier), one atomicAdd per (block, column)
+  if (mask_src) {
+    float* red = reinterpret_cast<float*>(&Ad[0][0]);  // [4 waves][CI]
+    static_assert(sizeof(Ad) >= 4 * CI * sizeof(float), "reduction fits Ad");
+    for (int ni = 0; ni < NFRAG; ++ni) {
+      float s = colsum[ni];
+      s += __shfl_xor(s, 16);
+      s += __shfl_xor(s, 32);
+      if (lane < 16) red[wave * CI + ni * 16 + lane] = s;
+    }
+    __syncthreads();
+    if (tid < CI) {
+      const float s =
+          red[tid] + red[CI + tid] + red[2 * CI + tid] + red[3 * CI + tid];
+      const int bid = blockIdx.y * gridDim.x + blockIdx.x;
+      atomicAdd(&dbias_slots[(bid & (DRLA_DBIAS_SLOTS - 1)) *
+                                 DRLA_DBIAS_STRIDE +
+                             tid], s);
     }
   }
 }
 
 CONV_KERNEL drla_conv_dgrad_l2(
-    const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch) {
-  conv_dgrad_impl<DRLA_CONV_GEOM(2)>(dy, w, dx, batch);
+    const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch,
+    const bf16raw* mask_src, float* dbias_slots) {
+  conv_dgrad_impl<DRLA_CONV_GEOM(2)>(dy, w, dx, batch, mask_src, dbias_slots);
 }
 CONV_KERNEL drla_conv_dgrad_l3(
-    const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch) {
-  conv_dgrad_impl<DRLA_CONV_GEOM(3)>(dy, w, dx, batch);
+    const bf16raw* dy, const bf16raw* w, bf16raw* dx, int batch,
+    const bf16raw* mask_src, float* dbias_slots) {
+  conv_dgrad_impl<DRLA_CONV_GEOM(3)>(dy, w, dx, batch, mask_src, dbias_slots);
 }

@@ -16,12 +16,24 @@ typedef __attribute__((ext_vector_type(4))) unsigned short ushort4v;
 // squared-norm partials: 16 slots, each on its own 64 B cache line
 // (buffer length = 16*16 floats; slot s lives at [s*16])
 #define DRLA_NORM_SLOTS 16
-// conv bias-grad partials: drla_relu_mask_bwd spreads its atomics over
-// DRLA_DBIAS_SLOTS rows of DRLA_DBIAS_STRIDE (>= max CO) floats;
-// drla_wgrad_finalize sums and re-zeroes them
+// conv bias-grad partials: drla_relu_mask_bwd and the masked dgrad epilogue
+// spread their atomics over DRLA_DBIAS_SLOTS rows of DRLA_DBIAS_STRIDE
+// (>= max CO) floats; drla_wgrad_finalize sums and re-zeroes them
 #define DRLA_DBIAS_SLOTS 16
 #define DRLA_DBIAS_STRIDE 64
 #define DRLA_BLOCK 256
+
+// drla_wgrad_finalize: one job per blockIdx.y (a conv layer's f32 [K][CO]
+// wgrad scratch and bias-grad slot set -> bf16 dW [CO][K] and dbias [CO])
+#define DRLA_FINALIZE_MAX_JOBS 4
+struct DrlaWgradFinalizeJobs {
+  float* scratch[DRLA_FINALIZE_MAX_JOBS];
+  bf16raw* dw[DRLA_FINALIZE_MAX_JOBS];
+  float* dbias_slots[DRLA_FINALIZE_MAX_JOBS];
+  bf16raw* dbias[DRLA_FINALIZE_MAX_JOBS];
+  int K[DRLA_FINALIZE_MAX_JOBS];
+  int CO[DRLA_FINALIZE_MAX_JOBS];
+};
 
 // ---- shapes the host launch code and the kernels must agree on ------------
 

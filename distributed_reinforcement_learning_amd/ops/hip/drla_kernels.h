@@ -113,18 +113,18 @@ DRLA_KERNEL drla_conv_fwd_l3(const bf16raw*, const bf16raw*, const bf16raw*,
 DRLA_KERNEL drla_relu_mask_bwd(const bf16raw*, const bf16raw*, bf16raw*,
                                float*, long long, int, long long, long long,
                                long long);
-DRLA_KERNEL drla_wgrad_finalize(float*, bf16raw*, int, int, float*,
-                                bf16raw*);
+DRLA_KERNEL drla_wgrad_finalize(DrlaWgradFinalizeJobs);
 DRLA_KERNEL drla_conv_wgrad_l1(const unsigned char*, const bf16raw*, float*,
                                int);
 DRLA_KERNEL drla_conv_wgrad_l1_c1(const unsigned char*, const bf16raw*,
                                   float*, int);
 DRLA_KERNEL drla_conv_wgrad_l2(const bf16raw*, const bf16raw*, float*, int);
 DRLA_KERNEL drla_conv_wgrad_l3(const bf16raw*, const bf16raw*, float*, int);
+// dgrad: dy, w, dx, batch, mask_src / null, bias-grad slot set / null
 DRLA_KERNEL drla_conv_dgrad_l2(const bf16raw*, const bf16raw*, bf16raw*,
-                               int);
+                               int, const bf16raw*, float*);
 DRLA_KERNEL drla_conv_dgrad_l3(const bf16raw*, const bf16raw*, bf16raw*,
-                               int);
+                               int, const bf16raw*, float*);
 
 // ---- conv3x3.hip (geometry order = DRLA_CONV3_LAYERS) ---------------------
 // fwd and dgrad: in, w, bias, mask, residual/addend, out, batch, relu_in
