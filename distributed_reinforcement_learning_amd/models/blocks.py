@@ -252,7 +252,7 @@ class LSTMCellTF(nn.Module):
             n = parts[0].shape[0]
             xh = torch.cat(parts + [self._ones_col(n, dtype,
                                                    parts[0].device)], dim=1)
-            g = torch.mm(xh, _AugGateWeight.apply(self.weight, self.bias))
+            g = self._aug_gemm(xh)
         else:
             xh = torch.cat(parts, dim=1)
             g = self.gates_from_xh(xh)
@@ -263,14 +263,27 @@ class LSTMCellTF(nn.Module):
             return lstm_fused_step(g, c.float(), self.forget_bias)
         return lstm_fused_step(g.float(), c.float(), self.forget_bias)
 
-    def forward_slab(self, xh: torch.Tensor, c: torch.Tensor):
+    def _aug_gemm(self, xh: torch.Tensor, grad_cols=None) -> torch.Tensor:
+        """xh @ [W ; b ; pad]: the hand-written gate GEMM
+        (ops/gate_gemm_op.py) when it takes the operands, else torch.mm.
+        grad_cols: the leading xh columns whose gradient anybody reads."""
+        from distributed_reinforcement_learning_amd.ops.gate_gemm_op import (
+            gate_gemm, gate_gemm_ok,
+        )
+        w_aug = _AugGateWeight.apply(self.weight, self.bias)
+        if gate_gemm_ok(xh, w_aug):
+            return gate_gemm(xh, w_aug, grad_cols)
+        return torch.mm(xh, w_aug)
+
+    def forward_slab(self, xh: torch.Tensor, c: torch.Tensor,
+                     grad_cols=None):
         """xh already assembled as [x | h | ones-pad] bf16 (ops/xh_op.py;
         requires _aug_weight_ok()): the same GEMM forward_cat runs, without
-        its cat and cast."""
+        its cat and cast. grad_cols: see _aug_gemm."""
         from distributed_reinforcement_learning_amd.ops.lstm_op import (
             lstm_fused_step,
         )
-        g = torch.mm(xh, _AugGateWeight.apply(self.weight, self.bias))
+        g = self._aug_gemm(xh, grad_cols)
         return lstm_fused_step(g, c.float(), self.forget_bias)
 
     def forward_xh(self, xh: torch.Tensor, c: torch.Tensor):

@@ -96,7 +96,9 @@ class ImpalaActorCritic(nn.Module):
             emb = self.action_emb.forward_into(flat_pa, slab, n_conv,
                                                flat_h.contiguous())
             xh = xh_op.assemble_xh(conv_y, emb, slab)
-            new_h, _ = self.lstm.forward_slab(xh, flat_c)
+            # _AssembleXh.backward drops the h and pad columns of dxh
+            new_h, _ = self.lstm.forward_slab(
+                xh, flat_c, grad_cols=n_conv + self.action_emb.out_features)
             return new_h, B, T
         conv_out = self.conv(flat_state)
         emb = self.action_emb(flat_pa)

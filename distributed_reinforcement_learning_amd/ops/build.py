@@ -33,6 +33,7 @@ SOURCES = [
     "conv.hip",
     "conv3x3.hip",
     "maxpool.hip",
+    "gate_gemm.hip",
     "per_tree.hip",
     "dqn_loss.hip",
     "a2c_loss.hip",

@@ -1716,6 +1716,101 @@ torch::Tensor maxpool3s2_bwd(const torch::Tensor& dy, const torch::Tensor& tap,
   return dx;
 }
 
+// ---- LSTM gate GEMM (gate_gemm.hip) ----------------------------------------
+// Operands are 2-D bf16 with unit column stride; the row stride is passed to
+// the kernels, so the xh slab and the as_strided augmented weight are read
+// in place. A lane moves 8 columns (16 bytes) at once: columns come in
+// multiples of 8 and every row starts at a multiple of 16 bytes.
+struct GgOperand { const bf16raw* p; long long ld; };
+GgOperand gg_operand(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2, name, " must be a 2-D GPU tensor");
+  const bf16raw* p = bf16_ptr(t, name);
+  const int64_t rows = t.size(0), cols = t.size(1);
+  TORCH_CHECK(cols >= 8 && cols % 8 == 0, name,
+              ": the column count must be a positive multiple of 8");
+  TORCH_CHECK(rows < (int64_t(1) << 30) && cols < (int64_t(1) << 30), name,
+              ": too large for the gate GEMM kernels");
+  const int64_t ld = rows > 1 ? t.stride(0) : cols;
+  TORCH_CHECK(t.stride(1) == 1 && ld >= cols, name,
+              " must have unit column stride and non-overlapping rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 8 == 0, name,
+              ": every row must start at a multiple of 16 bytes");
+  return {p, ld};
+}
+dim3 gg_grid(int64_t rows, int64_t cols, int mt, int split = 1) {
+  return dim3((cols + DRLA_GG_BN - 1) / DRLA_GG_BN,
+              (rows + 64 * mt - 1) / (64 * mt), split);
+}
+
+// forward split-K: enough splits to put about two blocks on each of the 256
+// CUs, each split keeping at least four 64-k chunks
+// (profiles/gate_gemm_r10.md)
+int gate_gemm_split(int64_t M, int64_t K, int64_t N) {
+  TORCH_CHECK(M >= 0 && K >= 8 && N >= 8, "gate GEMM: bad shape");
+  const dim3 g = gg_grid(std::max<int64_t>(M, 1), N, DRLA_GG_FWD_MT);
+  const int64_t tiles = (int64_t)g.x * g.y;
+  const int64_t chunks = (K + DRLA_GG_BK - 1) / DRLA_GG_BK;
+  const int64_t s = std::min<int64_t>(512 / tiles, chunks / 4);
+  return (int)std::clamp<int64_t>(s, 1, DRLA_GG_MAX_SPLIT);
+}
+
+// g [M, N] = xh [M, K] @ w [K, N]; split = 0: gate_gemm_split
+torch::Tensor gate_gemm_fwd(const torch::Tensor& xh, const torch::Tensor& w,
+                            int64_t split) {
+  const GgOperand a = gg_operand(xh, "xh"), b = gg_operand(w, "w");
+  const int64_t M = xh.size(0), K = xh.size(1), N = w.size(1);
+  TORCH_CHECK(w.size(0) == K, "w must be [xh columns, N]");
+  TORCH_CHECK(split >= 0 && split <= DRLA_GG_MAX_SPLIT, "split out of range");
+  auto g = torch::empty({M, N}, xh.options());
+  if (M == 0) return g;
+  const int S = split > 0 ? (int)split : gate_gemm_split(M, K, N);
+  torch::Tensor ws;
+  if (S > 1) ws = torch::empty({S, M, N}, xh.options().dtype(torch::kFloat));
+  hipLaunchKernelGGL(drla_gate_gemm_fwd, gg_grid(M, N, DRLA_GG_FWD_MT, S),
+                     dim3(DRLA_GG_BLOCK), 0, cur_stream(), a.p, a.ld, b.p,
+                     b.ld, BF16PM(g), S > 1 ? ws.data_ptr<float>() : nullptr,
+                     (int)M, (int)K, (int)N);
+  if (S > 1) {
+    const long long n4 = M * N / 4;
+    hipLaunchKernelGGL(drla_gate_gemm_reduce, dim3(drla_grid(n4)),
+                       dim3(DRLA_GG_BLOCK), 0, cur_stream(),
+                       static_cast<const float*>(ws.data_ptr<float>()),
+                       BF16PM(g), n4, S);
+  }
+  return g;
+}
+
+// dxh [M, K] = dg [M, N] @ w [K, N]^T, zero at columns >= grad_cols
+torch::Tensor gate_gemm_dgrad(const torch::Tensor& dg, const torch::Tensor& w,
+                              int64_t grad_cols) {
+  const GgOperand a = gg_operand(dg, "dg"), b = gg_operand(w, "w");
+  const int64_t M = dg.size(0), N = dg.size(1), K = w.size(0);
+  TORCH_CHECK(w.size(1) == N && K >= 8 && K % 8 == 0,
+              "w must be [K, dg columns] with K a positive multiple of 8");
+  TORCH_CHECK(grad_cols >= 0 && grad_cols <= K, "grad_cols out of range");
+  auto dxh = torch::empty({M, K}, dg.options());
+  if (M == 0) return dxh;
+  hipLaunchKernelGGL(drla_gate_gemm_dgrad, gg_grid(M, K, DRLA_GG_DGRAD_MT),
+                     dim3(DRLA_GG_BLOCK), 0, cur_stream(), a.p, a.ld, b.p,
+                     b.ld, BF16PM(dxh), (int)M, (int)K, (int)N,
+                     (int)grad_cols);
+  return dxh;
+}
+
+// dw [K, N] = xh [M, K]^T @ dg [M, N]
+torch::Tensor gate_gemm_wgrad(const torch::Tensor& xh,
+                              const torch::Tensor& dg) {
+  const GgOperand a = gg_operand(xh, "xh"), b = gg_operand(dg, "dg");
+  const int64_t M = xh.size(0), K = xh.size(1), N = dg.size(1);
+  TORCH_CHECK(dg.size(0) == M, "xh and dg must have the same rows");
+  if (M == 0) return torch::zeros({K, N}, xh.options());
+  auto dw = torch::empty({K, N}, xh.options());
+  hipLaunchKernelGGL(drla_gate_gemm_wgrad, gg_grid(K, N, DRLA_GG_WGRAD_MT),
+                     dim3(DRLA_GG_BLOCK), 0, cur_stream(), a.p, a.ld, b.p,
+                     b.ld, BF16PM(dw), (int)M, (int)K, (int)N);
+  return dw;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1773,6 +1868,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "3x3/2 max-pool backward: gather of dy by tap (+ addend)",
         py::arg("dy"), py::arg("tap"), py::arg("H"), py::arg("W"),
         py::arg("addend") = py::none());
+  // underscore: reached through ops/gate_gemm_op.py only
+  m.def("_gate_gemm_fwd", &gate_gemm_fwd,
+        "LSTM gate GEMM xh @ w (split = 0: the launcher's rule)",
+        py::arg("xh"), py::arg("w"), py::arg("split") = 0);
+  m.def("_gate_gemm_dgrad", &gate_gemm_dgrad,
+        "dg @ w^T, zero at columns >= grad_cols",
+        py::arg("dg"), py::arg("w"), py::arg("grad_cols"));
+  m.def("_gate_gemm_wgrad", &gate_gemm_wgrad, "xh^T @ dg",
+        py::arg("xh"), py::arg("dg"));
+  m.def("_gate_gemm_split", &gate_gemm_split,
+        "K-split of the gate GEMM forward for a shape",
+        py::arg("M"), py::arg("K"), py::arg("N"));
   m.def("dqn_loss_fwd", &dqn_loss_fwd,
         "fused double-DQN target + IS-weighted TD loss (K8)");
   m.def("dqn_loss_bwd", &dqn_loss_bwd, "closed-form K8 backward");

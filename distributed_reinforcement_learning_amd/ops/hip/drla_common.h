@@ -100,6 +100,16 @@ static_assert(drla_pool_fwd_lds_bytes(DRLA_POOL_MAX_ROW_ELEMS, 1, 1) <=
                   64 * 1024,
               "the widest row still fits one forward tile");
 
+// LSTM gate GEMM (gate_gemm.hip): a block owns 64 * MT rows x DRLA_GG_BN
+// columns and walks k in chunks of DRLA_GG_BK; grid = (N tiles, M tiles, S)
+#define DRLA_GG_BLOCK 256
+#define DRLA_GG_BN 64
+#define DRLA_GG_BK 64
+#define DRLA_GG_FWD_MT 1
+#define DRLA_GG_DGRAD_MT 2
+#define DRLA_GG_WGRAD_MT 2
+#define DRLA_GG_MAX_SPLIT 16
+
 // fused V-trace loss: T sizes the LDS scan buffers, A is the softmax width
 #define VT_MAX_T 128
 #define VT_MAX_A 64

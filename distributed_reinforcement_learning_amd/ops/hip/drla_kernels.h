@@ -173,6 +173,19 @@ DRLA_KERNEL drla_maxpool3s2_bwd_c32(const bf16raw*, const unsigned char*,
                                     const bf16raw*, bf16raw*, int, int, int,
                                     int, int, int);
 
+// ---- gate_gemm.hip (bf16, row strides in elements) ------------------------
+// fwd: xh, ldx, w, ldw, g, split workspace / null, M, K, N
+DRLA_KERNEL drla_gate_gemm_fwd(const bf16raw*, long long, const bf16raw*,
+                               long long, bf16raw*, float*, int, int, int);
+// dgrad: dg, lddg, w, ldw, dxh, M, K, N, grad_cols
+DRLA_KERNEL drla_gate_gemm_dgrad(const bf16raw*, long long, const bf16raw*,
+                                 long long, bf16raw*, int, int, int, int);
+// wgrad: xh, ldx, dg, lddg, dw, M, K, N
+DRLA_KERNEL drla_gate_gemm_wgrad(const bf16raw*, long long, const bf16raw*,
+                                 long long, bf16raw*, int, int, int);
+// reduce: workspace [S][M*N], g, M*N/4, S
+DRLA_KERNEL drla_gate_gemm_reduce(const float*, bf16raw*, long long, int);
+
 // ---- per_tree.hip ---------------------------------------------------------
 DRLA_KERNEL drla_per_update(float*, const long long*, const float*, int,
                             long long);
