@@ -132,7 +132,8 @@ class Agent(AgentBase):
         else:
             with torch.no_grad():
                 next_target_q = self.target_model(ns, a)
-        qs = self.model(torch.cat([s, ns]), torch.cat([pa, a]))
+        # rows B onward are detached below: the head's backward skips them
+        qs = self.model(torch.cat([s, ns]), torch.cat([pa, a]), grad_rows=B)
         main_q = qs[:B]
         next_main_q = qs[B:].detach()
         if side is not None:

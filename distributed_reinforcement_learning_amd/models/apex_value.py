@@ -14,6 +14,8 @@ scopes 'main' / 'target' (apex_value.py:44-63).
 
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -21,6 +23,7 @@ import torch.nn.functional as F
 from distributed_reinforcement_learning_amd.models.blocks import (
     ActionEmbedding, AtariConvStack, MLPHead,
 )
+from distributed_reinforcement_learning_amd.ops import dueling_q_op
 
 
 class ApexDuelingQ(nn.Module):
@@ -35,10 +38,18 @@ class ApexDuelingQ(nn.Module):
         self.value_branch = MLPHead(feat, list(hidden_list), num_action, None)
         self.mean_branch = MLPHead(feat, list(hidden_list), 1, None)
 
-    def forward(self, state: torch.Tensor, prev_action: torch.Tensor):
-        """state [N,84,84,C] normalized NHWC float; returns Q [N,A]."""
+    def forward(self, state: torch.Tensor, prev_action: torch.Tensor,
+                grad_rows: Optional[int] = None):
+        """state [N,84,84,C] normalized NHWC float; returns Q [N,A].
+        grad_rows: the caller uses the gradient of the leading grad_rows rows
+        of Q only (it detaches the rest); the fused head (ops/dueling_q_op.py)
+        then skips the dead rows in its backward. Default: all rows."""
         feat = torch.cat(
             [self.conv(state), self.action_emb(prev_action)], dim=1)
+        if dueling_q_op.dueling_q_ok(feat, self.value_branch,
+                                     self.mean_branch):
+            return dueling_q_op.dueling_q(feat, self.value_branch,
+                                          self.mean_branch, grad_rows)
         return self.value_branch(feat) - self.mean_branch(feat)
 
 
@@ -55,7 +66,9 @@ class VectorDuelingQ(nn.Module):
         self.value_out = nn.Linear(hidden, num_action)
         self.mean_out = nn.Linear(hidden, 1)
 
-    def forward(self, state: torch.Tensor, prev_action: torch.Tensor):
+    def forward(self, state: torch.Tensor, prev_action: torch.Tensor,
+                grad_rows: Optional[int] = None):
+        # grad_rows: accepted for the agent's sake, nothing here uses it
         state = state.to(self.obs_mlp[0].weight.dtype)
         feat = torch.cat(
             [self.obs_mlp(state), self.action_emb(prev_action)], dim=1)

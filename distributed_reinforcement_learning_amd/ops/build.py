@@ -34,6 +34,7 @@ SOURCES = [
     "conv3x3.hip",
     "maxpool.hip",
     "gate_gemm.hip",
+    "dueling_q.hip",
     "per_tree.hip",
     "dqn_loss.hip",
     "a2c_loss.hip",

@@ -1811,6 +1811,180 @@ torch::Tensor gate_gemm_wgrad(const torch::Tensor& xh,
   return dw;
 }
 
+// ---- Ape-X dueling Q head (dueling_q.hip) ----------------------------------
+// A branch arrives as its six parameters in nn.Linear layout, read in place:
+// W1 [256, K], b1 [256], W2 [256, 256], b2 [256], W3 [out, 256], b3 [out].
+struct DqBranch { const bf16raw *w1, *b1, *w2, *b2, *w3, *b3; };
+DqBranch dq_branch(const std::vector<torch::Tensor>& p, int64_t K,
+                   int64_t out, const char* name) {
+  TORCH_CHECK(p.size() == 6, name, ": six parameters (W1 b1 W2 b2 W3 b3)");
+  const int64_t H = DRLA_DQ_HID;
+  TORCH_CHECK(p[0].dim() == 2 && p[2].dim() == 2 && p[0].size(0) == H &&
+                  p[2].size(0) == H && p[2].size(1) == H,
+              name, ": hidden_list must be (256, 256)");
+  const int64_t want[6][2] = {{H, K}, {H, -1}, {H, H}, {H, -1}, {out, H},
+                              {out, -1}};
+  const bf16raw* ptr[6];
+  for (int i = 0; i < 6; ++i) {
+    check_gpu_contig(p[i], name);
+    const bool ok = want[i][1] < 0
+        ? p[i].dim() == 1 && p[i].size(0) == want[i][0]
+        : p[i].dim() == 2 && p[i].size(0) == want[i][0] &&
+              p[i].size(1) == want[i][1];
+    TORCH_CHECK(ok, name, ": parameter ", i, " has the wrong shape");
+    ptr[i] = bf16_ptr(p[i], name);
+    // W3's rows and the 256-long vectors are read 8 or 16 bytes at a time
+    TORCH_CHECK(i == 5 || reinterpret_cast<uintptr_t>(ptr[i]) % 16 == 0,
+                name, ": parameter ", i, " must be 16-byte aligned");
+  }
+  return {ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], ptr[5]};
+}
+// feat [N, K]: unit column stride, K a positive multiple of 8, rows 16-byte
+// aligned. Returns its row stride.
+int64_t dq_feat_ld(const torch::Tensor& feat) {
+  TORCH_CHECK(feat.is_cuda() && feat.dim() == 2, "feat must be a 2-D GPU tensor");
+  const bf16raw* p = bf16_ptr(feat, "feat");
+  const int64_t N = feat.size(0), K = feat.size(1);
+  TORCH_CHECK(K >= 8 && K % 8 == 0,
+              "feat: the column count must be a positive multiple of 8");
+  TORCH_CHECK(N < (int64_t(1) << 22) && K < (int64_t(1) << 22),
+              "feat: too large for the dueling head kernels");
+  const int64_t ld = N > 1 ? feat.stride(0) : K;
+  TORCH_CHECK(feat.stride(1) == 1 && ld >= K,
+              "feat must have unit column stride and non-overlapping rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 8 == 0,
+              "feat: every row must start at a multiple of 16 bytes");
+  return ld;
+}
+int64_t dq_actions(const std::vector<torch::Tensor>& vb) {
+  TORCH_CHECK(vb.size() == 6 && vb[4].dim() == 2, "value branch: six parameters");
+  const int64_t A = vb[4].size(0);
+  TORCH_CHECK(A >= 1 && A <= DRLA_DQ_MAX_A, "the dueling head kernels take 1 to ",
+              DRLA_DQ_MAX_A, " actions, got ", A);
+  return A;
+}
+
+// first layer's K-split: the 8 column tiles x row tiles are far fewer than
+// the CUs, so split K, up to about two blocks on each of the 256 CUs. Every
+// split keeps at least eight 64-k chunks: the gate GEMM's rule with four (S =
+// 13 at K = 3392) measured slower than S = 6, because the tail's prologue
+// reads the S slices (profiles/dueling_q_r11.md)
+int dq_l1_split(int64_t N, int64_t K) {
+  TORCH_CHECK(N >= 0 && K >= 8, "dueling head: bad shape");
+  const int64_t tiles = 8 * ((std::max<int64_t>(N, 1) + 63) / 64);
+  const int64_t chunks = (K + 63) / 64;
+  const int64_t s = std::min<int64_t>(512 / tiles, chunks / 8);
+  return (int)std::clamp<int64_t>(s, 1, DRLA_DQ_MAX_SPLIT);
+}
+
+// Q [N, A]. grad_rows < 0: nothing else is stored. Otherwise also z1, z2
+// [2, grad_rows, 256], W2^T [2, 256, 256] and W3v^T [256, 32] for the
+// backward. split = 0: dq_l1_split.
+std::vector<torch::Tensor> dq_head_fwd(const torch::Tensor& feat,
+                                       const std::vector<torch::Tensor>& vb,
+                                       const std::vector<torch::Tensor>& mb,
+                                       int64_t grad_rows, int64_t split) {
+  const int64_t ld = dq_feat_ld(feat);
+  const int64_t N = feat.size(0), K = feat.size(1), A = dq_actions(vb);
+  const DqBranch v = dq_branch(vb, K, A, "value branch");
+  const DqBranch m = dq_branch(mb, K, 1, "mean branch");
+  TORCH_CHECK(grad_rows <= N, "grad_rows out of range");
+  TORCH_CHECK(split >= 0 && split <= DRLA_DQ_MAX_SPLIT, "split out of range");
+  const bool train = grad_rows >= 0;
+  const int64_t G = std::max<int64_t>(grad_rows, 0), H = DRLA_DQ_HID;
+  auto q = torch::empty({N, A}, feat.options());
+  torch::Tensor z1, z2, w2t, w3t;
+  if (train) {
+    z1 = torch::empty({2, G, H}, feat.options());
+    z2 = torch::empty({2, G, H}, feat.options());
+    w2t = torch::empty({2, H, H}, feat.options());
+    w3t = torch::empty({H, DRLA_DQ_MAX_A}, feat.options());
+  }
+  if (N == 0) return {q, z1, z2, w2t, w3t};
+  const bool stash = train && G > 0;
+  const int S = split > 0 ? (int)split : dq_l1_split(N, K);
+  auto ws = torch::empty({S, N, 2 * H}, feat.options().dtype(torch::kFloat));
+  hipLaunchKernelGGL(drla_dq_l1_fwd, dim3(8, (N + 63) / 64, S),
+                     dim3(DRLA_DQ_BLOCK), 0, cur_stream(), BF16P(feat),
+                     (long long)ld, v.w1, m.w1, ws.data_ptr<float>(), (int)N,
+                     (int)K, v.w2, m.w2, v.w3, (int)A,
+                     stash ? BF16PM(w2t) : nullptr,
+                     stash ? BF16PM(w3t) : nullptr);
+  hipLaunchKernelGGL(drla_dq_tail_fwd,
+                     dim3((N + DRLA_DQ_BM - 1) / DRLA_DQ_BM),
+                     dim3(DRLA_DQ_TAIL_BLOCK), 0, cur_stream(),
+                     static_cast<const float*>(ws.data_ptr<float>()), S, v.b1,
+                     m.b1, v.w2, v.b2, m.w2, m.b2, v.w3, v.b3, m.w3, m.b3,
+                     BF16PM(q), stash ? BF16PM(z1) : nullptr,
+                     stash ? BF16PM(z2) : nullptr, (int)N, (int)A, (int)G);
+  return {q, z1, z2, w2t, w3t};
+}
+
+// dq [N, A] (rows >= grad_rows are not read) -> dfeat [N, K], then dW1 db1
+// dW2 db2 dW3 db3 of the value branch and of the mean branch
+std::vector<torch::Tensor> dq_head_bwd(
+    const torch::Tensor& dq, const torch::Tensor& feat,
+    const torch::Tensor& z1, const torch::Tensor& z2,
+    const torch::Tensor& w2t, const torch::Tensor& w3t,
+    const torch::Tensor& w1v, const torch::Tensor& w1m,
+    const torch::Tensor& w3m, int64_t grad_rows) {
+  const int64_t ld = dq_feat_ld(feat);
+  const int64_t N = feat.size(0), K = feat.size(1), H = DRLA_DQ_HID;
+  const int64_t G = grad_rows;
+  check_all_gpu_contig("dueling head backward operand", dq, z1, z2, w2t, w3t,
+                       w1v, w1m, w3m);
+  TORCH_CHECK(dq.dim() == 2 && dq.size(0) == N, "dq must be [N, A]");
+  const int64_t A = dq.size(1);
+  TORCH_CHECK(A >= 1 && A <= DRLA_DQ_MAX_A, "dq: 1 to 32 actions");
+  TORCH_CHECK(G >= 0 && G <= N, "grad_rows out of range");
+  TORCH_CHECK(z1.numel() == 2 * G * H && z2.numel() == 2 * G * H &&
+                  w2t.numel() == 2 * H * H &&
+                  w3t.numel() == H * DRLA_DQ_MAX_A && w1v.numel() == H * K &&
+                  w1m.numel() == H * K && w3m.numel() == H,
+              "dueling head backward: operand sizes do not fit");
+  for (const torch::Tensor* t : {&w1v, &w1m, &w3m}) {
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "dueling head backward: weights must be 16-byte aligned");
+  }
+  const auto o = feat.options();
+  // no live row: every gradient is zero and nothing is launched
+  std::vector<torch::Tensor> r;
+  auto out = [&](std::vector<int64_t> shape) {
+    r.push_back(G == 0 ? torch::zeros(shape, o) : torch::empty(shape, o));
+    return BF16PM(r.back());
+  };
+  out({N, K});
+  DrlaDqGrads g;
+  for (int c = 0; c < 2; ++c) {
+    const int64_t n3 = c ? 1 : A;
+    g.dw1[c] = out({H, K});
+    g.db1[c] = out({H});
+    g.dw2[c] = out({H, H});
+    g.db2[c] = out({H});
+    g.dw3[c] = out({n3, H});
+    g.db3[c] = out({n3});
+  }
+  if (G == 0) return r;
+  auto dz1 = torch::empty({2, G, H}, o), dz2 = torch::empty({2, G, H}, o);
+  auto d3m = torch::empty({G}, o);
+  hipLaunchKernelGGL(drla_dq_tail_bwd,
+                     dim3((G + DRLA_DQ_BM - 1) / DRLA_DQ_BM),
+                     dim3(DRLA_DQ_TAIL_BLOCK), 0, cur_stream(), BF16P(dq),
+                     BF16P(z1), BF16P(z2), BF16P(w2t), BF16P(w3t), BF16P(w3m),
+                     BF16PM(dz1), BF16PM(dz2), BF16PM(d3m), (int)A, (int)G);
+  const int64_t nk = (K + 63) / 64;
+  hipLaunchKernelGGL(drla_dq_wgrad, dim3(8 * nk + 32 + A + 1 + 5),
+                     dim3(DRLA_DQ_BLOCK), 0, cur_stream(), BF16P(feat),
+                     (long long)ld, BF16P(dz1), BF16P(dz2), BF16P(z1),
+                     BF16P(z2), BF16P(dq), BF16P(d3m), g, (int)K, (int)A,
+                     (int)G);
+  hipLaunchKernelGGL(drla_dq_l1_dgrad, dim3(nk, (N + 63) / 64),
+                     dim3(DRLA_DQ_BLOCK), 0, cur_stream(), BF16P(dz1),
+                     BF16P(w1v), BF16P(w1m), BF16PM(r[0]), (int)N, (int)K,
+                     (int)G);
+  return r;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1880,6 +2054,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_gate_gemm_split", &gate_gemm_split,
         "K-split of the gate GEMM forward for a shape",
         py::arg("M"), py::arg("K"), py::arg("N"));
+  // underscore: reached through ops/dueling_q_op.py only
+  m.def("_dq_head_fwd", &dq_head_fwd,
+        "Ape-X dueling Q head -> [Q, z1, z2, W2^T, W3v^T] (grad_rows < 0: Q "
+        "only; split = 0: the launcher's rule)",
+        py::arg("feat"), py::arg("value_branch"), py::arg("mean_branch"),
+        py::arg("grad_rows") = -1, py::arg("split") = 0);
+  m.def("_dq_head_bwd", &dq_head_bwd,
+        "dueling Q head backward -> [dfeat, value branch's dW1 db1 dW2 db2 "
+        "dW3 db3, mean branch's]",
+        py::arg("dq"), py::arg("feat"), py::arg("z1"), py::arg("z2"),
+        py::arg("w2t"), py::arg("w3t"), py::arg("w1v"), py::arg("w1m"),
+        py::arg("w3m"), py::arg("grad_rows"));
+  m.def("_dq_l1_split", &dq_l1_split,
+        "K-split of the dueling head's first layer for a shape",
+        py::arg("N"), py::arg("K"));
   m.def("dqn_loss_fwd", &dqn_loss_fwd,
         "fused double-DQN target + IS-weighted TD loss (K8)");
   m.def("dqn_loss_bwd", &dqn_loss_bwd, "closed-form K8 backward");

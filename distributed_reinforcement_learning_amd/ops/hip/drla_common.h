@@ -110,6 +110,25 @@ static_assert(drla_pool_fwd_lds_bytes(DRLA_POOL_MAX_ROW_ELEMS, 1, 1) <=
 #define DRLA_GG_WGRAD_MT 2
 #define DRLA_GG_MAX_SPLIT 16
 
+// Ape-X dueling Q head (dueling_q.hip): two K -> 256 -> 256 -> {A, 1} chains.
+// l1_fwd / wgrad / l1_dgrad: 64 x 64 tiles of DRLA_DQ_BLOCK threads; the
+// tails: DRLA_DQ_BM rows per block of DRLA_DQ_TAIL_BLOCK threads
+#define DRLA_DQ_HID 256
+#define DRLA_DQ_MAX_A 32
+#define DRLA_DQ_BLOCK 256
+#define DRLA_DQ_TAIL_BLOCK 512
+#define DRLA_DQ_BM 16
+#define DRLA_DQ_MAX_SPLIT 16
+// drla_dq_wgrad's outputs, [0] the value branch, [1] the mean branch
+struct DrlaDqGrads {
+  bf16raw* dw1[2];
+  bf16raw* dw2[2];
+  bf16raw* dw3[2];
+  bf16raw* db1[2];
+  bf16raw* db2[2];
+  bf16raw* db3[2];
+};
+
 // fused V-trace loss: T sizes the LDS scan buffers, A is the softmax width
 #define VT_MAX_T 128
 #define VT_MAX_A 64

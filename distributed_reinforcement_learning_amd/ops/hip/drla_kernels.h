@@ -186,6 +186,32 @@ DRLA_KERNEL drla_gate_gemm_wgrad(const bf16raw*, long long, const bf16raw*,
 // reduce: workspace [S][M*N], g, M*N/4, S
 DRLA_KERNEL drla_gate_gemm_reduce(const float*, bf16raw*, long long, int);
 
+// ---- dueling_q.hip (Ape-X head; v = value branch, m = mean branch) --------
+// l1_fwd: feat, ldf, w1v, w1m, ws, N, K, w2v, w2m, w3v, A, w2t / null, w3t
+DRLA_KERNEL drla_dq_l1_fwd(const bf16raw*, long long, const bf16raw*,
+                           const bf16raw*, float*, int, int, const bf16raw*,
+                           const bf16raw*, const bf16raw*, int, bf16raw*,
+                           bf16raw*);
+// tail_fwd: ws, S, b1v, b1m, w2v, b2v, w2m, b2m, w3v, b3v, w3m, b3m, q,
+// z1 stash / null, z2 stash, N, A, grad_rows
+DRLA_KERNEL drla_dq_tail_fwd(
+    const float*, int, const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, bf16raw*,
+    bf16raw*, int, int, int);
+// tail_bwd: dq, z1, z2, w2t, w3t, w3m, dz1, dz2, d3m, A, grad_rows
+DRLA_KERNEL drla_dq_tail_bwd(const bf16raw*, const bf16raw*, const bf16raw*,
+                             const bf16raw*, const bf16raw*, const bf16raw*,
+                             bf16raw*, bf16raw*, bf16raw*, int, int);
+// wgrad: feat, ldf, dz1, dz2, z1, z2, dq, d3m, outputs, K, A, grad_rows
+DRLA_KERNEL drla_dq_wgrad(const bf16raw*, long long, const bf16raw*,
+                          const bf16raw*, const bf16raw*, const bf16raw*,
+                          const bf16raw*, const bf16raw*, DrlaDqGrads, int,
+                          int, int);
+// l1_dgrad: dz1, w1v, w1m, dfeat, N, K, grad_rows
+DRLA_KERNEL drla_dq_l1_dgrad(const bf16raw*, const bf16raw*, const bf16raw*,
+                             bf16raw*, int, int, int);
+
 // ---- per_tree.hip ---------------------------------------------------------
 DRLA_KERNEL drla_per_update(float*, const long long*, const float*, int,
                             long long);
