@@ -18,12 +18,14 @@ import torch.nn.functional as F
 from distributed_reinforcement_learning_amd.models.blocks import (
     ActionEmbedding, AtariConvStack, LSTMCellTF,
 )
+from distributed_reinforcement_learning_amd.ops import r2d2_head_op
 from distributed_reinforcement_learning_amd.ops.lstm_op import (
     LSTM_SEQ_MAX_HIDDEN,
 )
 
-# widest LSTM output the one-launch dueling head stages in LDS
-# (ops/hip/drla_common.h DHEAD_MAX_IN)
+# widest LSTM output the older one-launch no-grad head stages in LDS
+# (ops/hip/drla_common.h DHEAD_MAX_IN); it serves q_window when the MFMA head
+# (ops/r2d2_head_op.py, H <= 512) is switched off or refuses the operands
 _DHEAD_MAX_IN = 256
 
 
@@ -107,6 +109,8 @@ class R2D2LstmQ(nn.Module):
                 w[F:].contiguous(), h0.float().contiguous(),
                 c0.float().contiguous(), seq_done.contiguous(),
                 self.lstm.forget_bias)
+            if r2d2_head_op.r2d2_head_ok(h_all, self.trunk, self.out):
+                return r2d2_head_op.r2d2_head(h_all, self.trunk, self.out)
             q = self._head(h_all.reshape(B * L, -1))
             return q.reshape(B, L, -1)
         if kern_ok:
@@ -123,13 +127,20 @@ class R2D2LstmQ(nn.Module):
                 xg.reshape(B, L, -1), w[F:], h0.float(), c0.float(),
                 seq_done, self.lstm.forget_bias)
             import os as _os
-            # fused train-head measured NET SLOWER than the torch chain
-            # (A/B same box: 22.2k -> 20.0k seq/s at 15/7 — the fused
-            # backward's serial per-row phases cost more than the ~13
-            # launches it saves); opt-in for round-3 tuning
+            # Three heads, in this order. DRLA_FUSED_DHEAD=1 asks for the
+            # scalar fused head of r2d2_loss.hip by name: it measured NET
+            # SLOWER than the torch chain (22.2k -> 20.0k seq/s at 15/7, its
+            # backward runs serial per-row phases) and stays opt-in. Else the
+            # MFMA head (1 launch forward, 2 backward) where r2d2_head_ok
+            # takes the operands and the trained use is switched on
+            # (KERNELS.md, "R2D2 dueling head"). Else the torch chain.
+            fused_opt_in = _os.environ.get("DRLA_FUSED_DHEAD") == "1"
+            if not fused_opt_in and r2d2_head_op.r2d2_head_ok(
+                    h_all, self.trunk, self.out):
+                return r2d2_head_op.r2d2_head(h_all, self.trunk, self.out)
             if (self.out.weight.dtype == torch.bfloat16
                     and self.trunk.weight.dtype == torch.bfloat16
-                    and _os.environ.get("DRLA_FUSED_DHEAD") == "1"):
+                    and fused_opt_in):
                 from distributed_reinforcement_learning_amd.ops import (
                     r2d2_op,
                 )
@@ -174,6 +185,10 @@ class R2D2LstmQ(nn.Module):
                 xg.reshape(B, L, -1).contiguous(), w[F_:].contiguous(),
                 h0.float().contiguous(), c0.float().contiguous(),
                 seq_done.contiguous(), self.lstm.forget_bias)
+            if r2d2_head_op.r2d2_head_ok(h_all, self.trunk, self.out):
+                # MFMA head: window slice and cast in-kernel, H <= 512
+                return r2d2_head_op.r2d2_head(h_all, self.trunk, self.out,
+                                              burn)
             if (self.out.weight.dtype == torch.bfloat16
                     and self.trunk.weight.dtype == torch.bfloat16
                     and self.lstm_size <= _DHEAD_MAX_IN):

@@ -58,10 +58,11 @@ from distributed_reinforcement_learning_amd.ops.optim import FusedRMSProp, Fused
 from distributed_reinforcement_learning_amd.ops.pool_op import max_pool3x3s2
 from distributed_reinforcement_learning_amd.ops.gate_gemm_op import gate_gemm, gate_gemm_ok
 from distributed_reinforcement_learning_amd.ops.dueling_q_op import dueling_q, dueling_q_ok
+from distributed_reinforcement_learning_amd.ops.r2d2_head_op import r2d2_head, r2d2_head_ok
 
 __all__ = [
     "available", "require_ext", "vtrace_scan", "fused_vtrace_loss",
     "normalize_frames", "lstm_fused_step", "FusedRMSProp", "FusedAdam",
     "max_pool3x3s2", "gate_gemm", "gate_gemm_ok", "dueling_q",
-    "dueling_q_ok",
+    "dueling_q_ok", "r2d2_head", "r2d2_head_ok",
 ]

@@ -35,6 +35,7 @@ SOURCES = [
     "maxpool.hip",
     "gate_gemm.hip",
     "dueling_q.hip",
+    "r2d2_head.hip",
     "per_tree.hip",
     "dqn_loss.hip",
     "a2c_loss.hip",

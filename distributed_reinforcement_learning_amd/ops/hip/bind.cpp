@@ -1985,6 +1985,118 @@ std::vector<torch::Tensor> dq_head_bwd(
   return r;
 }
 
+// ---- R2D2 dueling head (r2d2_head.hip) --------------------------------------
+// The two nn.Linear of the head, read in place: trunk [128, H] + [128], out
+// [A + 1, 128] + [A + 1]. Returns A.
+int64_t r2h_weights(const torch::Tensor& wt, const torch::Tensor& bt,
+                    const torch::Tensor& wo, const torch::Tensor& bo,
+                    int64_t H) {
+  check_all_gpu_contig("r2d2 head weight", wt, bt, wo, bo);
+  for (const torch::Tensor* t : {&wt, &bt, &wo, &bo}) {
+    bf16_ptr(*t, "r2d2 head weight");
+  }
+  TORCH_CHECK(wt.dim() == 2 && wt.size(0) == DRLA_R2H_MID && wt.size(1) == H &&
+                  bt.dim() == 1 && bt.size(0) == DRLA_R2H_MID,
+              "r2d2 head: the trunk must be [", DRLA_R2H_MID, ", ", H,
+              "] with its bias, got [", wt.size(0), ", ",
+              wt.dim() == 2 ? wt.size(1) : -1, "]");
+  TORCH_CHECK(wo.dim() == 2 && wo.size(1) == DRLA_R2H_MID && bo.dim() == 1 &&
+                  bo.size(0) == wo.size(0),
+              "r2d2 head: out must be [A + 1, ", DRLA_R2H_MID,
+              "] with its bias");
+  const int64_t A = wo.size(0) - 1;
+  TORCH_CHECK(A >= 1 && A < DRLA_R2H_MAX_AO, "the r2d2 head kernels take 1 to ",
+              DRLA_R2H_MAX_AO - 1, " actions, got ", A);
+  // rows of wt and wo and the trunk bias are read 8 or 16 bytes at a time
+  for (const torch::Tensor* t : {&wt, &bt, &wo}) {
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "r2d2 head: weights must be 16-byte aligned");
+  }
+  return A;
+}
+// h [.., H] f32, contiguous, rows 16-byte aligned, H a multiple of 8 in
+// [8, DRLA_R2H_MAX_H]. Returns H.
+int64_t r2h_hidden(const torch::Tensor& h, int64_t dims) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == dims &&
+                  h.scalar_type() == torch::kFloat && h.is_contiguous(),
+              "r2d2 head: h must be a contiguous f32 GPU tensor of ", dims,
+              " dimensions");
+  const int64_t H = h.size(dims - 1);
+  TORCH_CHECK(H >= 8 && H <= DRLA_R2H_MAX_H && H % 8 == 0,
+              "r2d2 head: the hidden size must be a multiple of 8 in [8, ",
+              DRLA_R2H_MAX_H, "], got ", H);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0,
+              "r2d2 head: every row of h must start at a multiple of 16 bytes");
+  TORCH_CHECK(h.numel() / H < (int64_t(1) << 22),
+              "r2d2 head: too many rows");
+  return H;
+}
+
+// h_all [B, L, H] -> Q [B, L - burn, A] of the steps from burn on; stash:
+// also z [B (L - burn), 128] for the backward (else undefined)
+std::vector<torch::Tensor> r2d2_head_fwd(
+    const torch::Tensor& h_all, const torch::Tensor& wt,
+    const torch::Tensor& bt, const torch::Tensor& wo, const torch::Tensor& bo,
+    int64_t burn, bool stash) {
+  const int64_t H = r2h_hidden(h_all, 3);
+  const int64_t A = r2h_weights(wt, bt, wo, bo, H);
+  const int64_t B = h_all.size(0), L = h_all.size(1);
+  TORCH_CHECK(burn >= 0 && burn <= L, "r2d2 head: burn outside [0, L]");
+  const int64_t W = L - burn, N = B * W;
+  const auto o = h_all.options().dtype(torch::kBFloat16);
+  auto q = torch::empty({B, W, A}, o);
+  torch::Tensor z;
+  if (stash) z = torch::empty({N, DRLA_R2H_MID}, o);
+  if (N == 0) return {q, z};
+  hipLaunchKernelGGL(drla_r2h_fwd, dim3((N + DRLA_R2H_BM - 1) / DRLA_R2H_BM),
+                     dim3(DRLA_R2H_BLOCK), 0, cur_stream(),
+                     static_cast<const float*>(h_all.data_ptr<float>()),
+                     BF16P(wt), BF16P(bt), BF16P(wo), BF16P(bo), BF16PM(q),
+                     stash ? BF16PM(z) : nullptr, (int)N, (int)W, (int)L,
+                     (int)burn, (int)H, (int)A);
+  return {q, z};
+}
+
+// dq [N, A], h [N, H] (the rows the forward read), z [N, 128] -> dh [N, H]
+// f32, dWt, dbt, dWo, dbo
+std::vector<torch::Tensor> r2d2_head_bwd(
+    const torch::Tensor& dq, const torch::Tensor& h, const torch::Tensor& z,
+    const torch::Tensor& wt, const torch::Tensor& wo) {
+  const int64_t H = r2h_hidden(h, 2), N = h.size(0), M = DRLA_R2H_MID;
+  check_all_gpu_contig("r2d2 head backward operand", dq, z, wt, wo);
+  TORCH_CHECK(wo.dim() == 2 && dq.dim() == 2 && dq.size(0) == N &&
+                  dq.size(1) == wo.size(0) - 1,
+              "r2d2 head backward: dq must be [N, A]");
+  const int64_t A = dq.size(1);
+  TORCH_CHECK(A >= 1 && A < DRLA_R2H_MAX_AO && wt.numel() == M * H &&
+                  wo.numel() == (A + 1) * M && z.numel() == N * M,
+              "r2d2 head backward: operand sizes do not fit");
+  for (const torch::Tensor* t : {&wt, &wo, &z}) {
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "r2d2 head backward: operands must be 16-byte aligned");
+  }
+  const auto o = dq.options();
+  // no row: every gradient is zero and nothing is launched
+  auto make = [&](std::vector<int64_t> shape, const torch::TensorOptions& to) {
+    return N == 0 ? torch::zeros(shape, to) : torch::empty(shape, to);
+  };
+  auto dh = make({N, H}, h.options());
+  auto dwt = make({M, H}, o), dbt = make({M}, o);
+  auto dwo = make({A + 1, M}, o), dbo = make({A + 1}, o);
+  if (N == 0) return {dh, dwt, dbt, dwo, dbo};
+  auto dy = torch::empty({N, DRLA_R2H_DY_LD}, o), dz = torch::empty({N, M}, o);
+  hipLaunchKernelGGL(drla_r2h_bwd, dim3((N + DRLA_R2H_BM - 1) / DRLA_R2H_BM),
+                     dim3(DRLA_R2H_BLOCK), 0, cur_stream(), BF16P(dq),
+                     BF16P(z), BF16P(wt), BF16P(wo), dh.data_ptr<float>(),
+                     BF16PM(dy), BF16PM(dz), (int)N, (int)H, (int)A);
+  hipLaunchKernelGGL(drla_r2h_wgrad, dim3(2 * ((H + 63) / 64) + 2),
+                     dim3(DRLA_R2H_BLOCK), 0, cur_stream(),
+                     static_cast<const float*>(h.data_ptr<float>()), BF16P(z),
+                     BF16P(dy), BF16P(dz), BF16PM(dwt), BF16PM(dbt),
+                     BF16PM(dwo), BF16PM(dbo), (int)N, (int)H, (int)A);
+  return {dh, dwt, dbt, dwo, dbo};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2069,6 +2181,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_dq_l1_split", &dq_l1_split,
         "K-split of the dueling head's first layer for a shape",
         py::arg("N"), py::arg("K"));
+  // underscore: reached through ops/r2d2_head_op.py only
+  m.def("_r2d2_head_fwd", &r2d2_head_fwd,
+        "R2D2 dueling head over the steps from burn on -> [Q, z or None]",
+        py::arg("h_all"), py::arg("wt"), py::arg("bt"), py::arg("wo"),
+        py::arg("bo"), py::arg("burn") = 0, py::arg("stash") = false);
+  m.def("_r2d2_head_bwd", &r2d2_head_bwd,
+        "R2D2 dueling head backward -> [dh, dWt, dbt, dWo, dbo]",
+        py::arg("dq"), py::arg("h"), py::arg("z"), py::arg("wt"),
+        py::arg("wo"));
   m.def("dqn_loss_fwd", &dqn_loss_fwd,
         "fused double-DQN target + IS-weighted TD loss (K8)");
   m.def("dqn_loss_bwd", &dqn_loss_bwd, "closed-form K8 backward");

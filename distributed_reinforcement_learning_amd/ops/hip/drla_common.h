@@ -129,6 +129,16 @@ struct DrlaDqGrads {
   bf16raw* db3[2];
 };
 
+// R2D2 dueling head (r2d2_head.hip): H -> 128 -> A + 1, DRLA_R2H_BM rows per
+// forward / backward block; the weight-gradient launch reads dy as
+// [N][DRLA_R2H_DY_LD], columns past A zero
+#define DRLA_R2H_MID 128
+#define DRLA_R2H_MAX_H 512
+#define DRLA_R2H_MAX_AO 64
+#define DRLA_R2H_DY_LD 64
+#define DRLA_R2H_BM 16
+#define DRLA_R2H_BLOCK 256
+
 // fused V-trace loss: T sizes the LDS scan buffers, A is the softmax width
 #define VT_MAX_T 128
 #define VT_MAX_A 64

@@ -212,6 +212,20 @@ DRLA_KERNEL drla_dq_wgrad(const bf16raw*, long long, const bf16raw*,
 DRLA_KERNEL drla_dq_l1_dgrad(const bf16raw*, const bf16raw*, const bf16raw*,
                              bf16raw*, int, int, int);
 
+// ---- r2d2_head.hip (R2D2 head; wt / bt = trunk, wo / bo = out) ------------
+// fwd: h_all, wt, bt, wo, bo, q, z stash / null, N, W, L, burn, H, A
+DRLA_KERNEL drla_r2h_fwd(const float*, const bf16raw*, const bf16raw*,
+                         const bf16raw*, const bf16raw*, bf16raw*, bf16raw*,
+                         int, int, int, int, int, int);
+// bwd: dq, z, wt, wo, dh, dy, dz, N, H, A
+DRLA_KERNEL drla_r2h_bwd(const bf16raw*, const bf16raw*, const bf16raw*,
+                         const bf16raw*, float*, bf16raw*, bf16raw*, int, int,
+                         int);
+// wgrad: h, z, dy, dz, dwt, dbt, dwo, dbo, N, H, A
+DRLA_KERNEL drla_r2h_wgrad(const float*, const bf16raw*, const bf16raw*,
+                           const bf16raw*, bf16raw*, bf16raw*, bf16raw*,
+                           bf16raw*, int, int, int);
+
 // ---- per_tree.hip ---------------------------------------------------------
 DRLA_KERNEL drla_per_update(float*, const long long*, const float*, int,
                             long long);
