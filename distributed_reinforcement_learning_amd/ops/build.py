@@ -41,6 +41,7 @@ SOURCES = [
     "a2c_loss.hip",
     "r2d2_loss.hip",
     "mlp_heads.hip",
+    "heads_bwd.hip",
 ]
 
 

@@ -1155,7 +1155,9 @@ std::vector<torch::Tensor> mlp_heads_fwd(
 }
 
 // ws_opt: the workspace a want_bwd_bufs forward already zeroed (one use per
-// forward: the kernel accumulates into it); absent -> zero-filled here
+// forward: the kernel adds the bias sums onto its tail, which must be zero;
+// the dh region in front is overwritten whatever it holds); absent -> made
+// here, the tail zero-filled
 std::vector<torch::Tensor> mlp_heads_bwd(
     torch::Tensor dlogits, torch::Tensor dvalue, torch::Tensor stash,
     std::vector<torch::Tensor> weights, int64_t A,
@@ -1171,8 +1173,8 @@ std::vector<torch::Tensor> mlp_heads_bwd(
   auto dz2p = torch::empty({N, 256}, bopt);
   auto dz1v = torch::empty({N, 256}, bopt);
   auto dz2v = torch::empty({N, 256}, bopt);
-  // dh + all six bias grads live in ONE zeroed workspace (atomics targets;
-  // one fill kernel instead of seven)
+  // dh + all six bias sums live in ONE workspace: dh is stored, the bias
+  // tail is the atomics' target
   const long long ws_n = (long long)N * 256 + 4 * 256 + A + 1;
   torch::Tensor ws;
   if (ws_opt.has_value()) {
@@ -1181,7 +1183,8 @@ std::vector<torch::Tensor> mlp_heads_bwd(
     TORCH_CHECK(ws.scalar_type() == torch::kFloat && ws.numel() == ws_n,
                 "ws must be f32 [N*256 + 4*256 + A + 1]");
   } else {
-    ws = torch::zeros({ws_n}, fopt);
+    ws = torch::empty({ws_n}, fopt);
+    ws.narrow(0, (long long)N * 256, ws_n - (long long)N * 256).zero_();
   }
   long long off = 0;
   auto dh = ws.narrow(0, off, (long long)N * 256).view({N, 256});
@@ -1193,7 +1196,7 @@ std::vector<torch::Tensor> mlp_heads_bwd(
   auto db2v = ws.narrow(0, off, 256); off += 256;
   auto db3v = ws.narrow(0, off, 1);
   hipLaunchKernelGGL(
-      drla_mlp_heads_bwd, dim3(mh_row_tiles(N), 2), dim3(256), 0,
+      drla_mlp_heads_bwd, dim3(mh_row_tiles(N)), dim3(512), 0,
       cur_stream(), BF16P(dlogits), dvalue.data_ptr<float>(), BF16P(stash),
       BF16P(weights[0]), BF16P(weights[1]), BF16P(weights[2]),
       BF16P(weights[3]), BF16P(weights[4]), BF16P(weights[5]), BF16PM(dz1p),

@@ -276,26 +276,30 @@ DRLA_KERNEL drla_dhead_train_bwd(
 DRLA_KERNEL drla_dhead_train_fin(const float*, bf16raw*, bf16raw*, bf16raw*,
                                  bf16raw*, int, int, int);
 
+// ---- heads_bwd.hip --------------------------------------------------------
+// drla_mlp_heads_bwd: grid ceil(N / MH_BM), 512 threads; drla_heads_wgrad:
+// grid 73, 256 threads
+DRLA_KERNEL drla_mlp_heads_bwd(
+    const bf16raw*, const float*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, bf16raw*, bf16raw*, bf16raw*, bf16raw*, float*, float*,
+    float*, float*, float*, float*, float*, int, int);
+DRLA_KERNEL drla_heads_wgrad(
+    const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
+    const bf16raw*, const float*, const bf16raw*, bf16raw*, bf16raw*,
+    bf16raw*, bf16raw*, bf16raw*, bf16raw*, const float*, bf16raw*,
+    bf16raw*, bf16raw*, bf16raw*, bf16raw*, bf16raw*, int, int);
+
 // ---- mlp_heads.hip --------------------------------------------------------
 DRLA_KERNEL drla_mlp_heads_fwd(
     const float*, const bf16raw*, const bf16raw*, const bf16raw*,
     const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
     const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
     const bf16raw*, bf16raw*, float*, bf16raw*, int, int, bf16raw*, float*);
-DRLA_KERNEL drla_mlp_heads_bwd(
-    const bf16raw*, const float*, const bf16raw*, const bf16raw*,
-    const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
-    const bf16raw*, bf16raw*, bf16raw*, bf16raw*, bf16raw*, float*, float*,
-    float*, float*, float*, float*, float*, int, int);
 DRLA_KERNEL drla_heads_wt_pack(const bf16raw*, const bf16raw*,
                                const bf16raw*, const bf16raw*,
                                const bf16raw*, const bf16raw*, bf16raw*,
                                int);
-DRLA_KERNEL drla_heads_wgrad(
-    const bf16raw*, const bf16raw*, const bf16raw*, const bf16raw*,
-    const bf16raw*, const float*, const bf16raw*, bf16raw*, bf16raw*,
-    bf16raw*, bf16raw*, bf16raw*, bf16raw*, const float*, bf16raw*,
-    bf16raw*, bf16raw*, bf16raw*, bf16raw*, bf16raw*, int, int);
 DRLA_KERNEL drla_embed_mlp_fwd(const long long*, const bf16raw*,
                                const bf16raw*, const bf16raw*,
                                const bf16raw*, bf16raw*, bf16raw*, int, int,

@@ -14,10 +14,8 @@
 //                                decode weights" row)
 //   B_op[k][col=row] = act[row][k]  (row-major LDS act image, vec8)
 // The epilogue un-transposes with scalar LDS writes (once per layer, not
-// per k-chunk). The backward dgrad chain uses the same shape on
-// Pre-TRANSPOSED weights (built by the autograd wrapper: 4 small .t()
-// copies), fusing ReLU masks and bias gradients; only the six
-// MFMA-efficient wgrad GEMMs stay on hipBLASLt.
+// per k-chunk). The heads' backward (dgrad chains and the six wgrads) is in
+// heads_bwd.hip; its dgrad chains read the W^T pack this file writes.
 
 #include "drla_kernels.h"
 
@@ -55,8 +53,8 @@
 //   mh_epilogue  un-transpose, bias / ReLU / mask, side outputs
 //
 // SIDE == MH_MASK: v *= (stash > 0), dz-global write + colsum bias partials
-// (backward layers). SIDE == MH_BIAS: v += bias, RELU applies (forward
-// layers). DH != null: terminal f32 row-grad output, added atomically.
+// (the embed backward). SIDE == MH_BIAS: v += bias, RELU applies (forward
+// layers). DH != null: f32 row-grad output, added atomically (unused now).
 template <int KCH>
 struct MhFrags {
   bf16x8 a[KCH][4];
@@ -373,183 +371,6 @@ extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_fwd(
   }
 }
 
-// The one-chunk-ahead form of the same pass in one function:
-// drla_mlp_heads_bwd keeps it, since requesting its chains' operands whole
-// buys that kernel nothing (KERNELS.md) and costs it a full register file.
-// Only the k-loop differs: the next chunk's fragments load while this
-// chunk's MFMAs run; the side values are requested behind the loop and the
-// epilogue is the shared one. M [nout][kdim] row-major, kdim a multiple of
-// 32; side_src: mask_stash [N,256] (MH_MASK), bias [nout] (MH_BIAS) or
-// unused (MH_NONE).
-template <bool RELU, int SIDE>
-__device__ void mh_pass(const bf16raw (*act_in)[MH_LD],
-                        bf16raw (*act_out)[MH_LD],
-                        const bf16raw* __restrict__ M,   // [nout][kdim]
-                        const bf16raw* __restrict__ side_src,
-                        bf16raw* __restrict__ dz_global,         // [N,256]
-                        float* __restrict__ colsum,              // [256]
-                        bf16raw* __restrict__ stash,     // [N,nout] or null
-                        float* __restrict__ dh_global,   // [N,256] or null
-                        int row0, int N, int nout, int kdim) {
-  const int lane = threadIdx.x % 64;
-  const int out0 = mh_out0();
-
-  f32x4 acc[4];
-  for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
-
-  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (out0 < nout) {
-    bf16x8 a_cur0, a_cur1, a_cur2, a_cur3;
-    const int kf = (lane >> 4) * 8;
-#define DRLA_MH_LOAD(ni, dst, k0)                                       \
-    {                                                                   \
-      const int orow = out0 + (ni) * 16 + (lane & 15);                  \
-      dst = (orow < nout)                                               \
-          ? *reinterpret_cast<const bf16x8*>(                           \
-                M + (long long)orow * kdim + (k0) + kf)                 \
-          : zero8;                                                      \
-    }
-    DRLA_MH_LOAD(0, a_cur0, 0); DRLA_MH_LOAD(1, a_cur1, 0);
-    DRLA_MH_LOAD(2, a_cur2, 0); DRLA_MH_LOAD(3, a_cur3, 0);
-    for (int k0 = 0; k0 < kdim; k0 += 32) {
-      bf16x8 a_nxt0, a_nxt1, a_nxt2, a_nxt3;
-      if (k0 + 32 < kdim) {
-        DRLA_MH_LOAD(0, a_nxt0, k0 + 32); DRLA_MH_LOAD(1, a_nxt1, k0 + 32);
-        DRLA_MH_LOAD(2, a_nxt2, k0 + 32); DRLA_MH_LOAD(3, a_nxt3, k0 + 32);
-      }
-      const bf16x8 b_frag =
-          *reinterpret_cast<const bf16x8*>(&act_in[lane & 15][k0 + kf]);
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur0, b_frag,
-                                                       acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur1, b_frag,
-                                                       acc[1], 0, 0, 0);
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur2, b_frag,
-                                                       acc[2], 0, 0, 0);
-      acc[3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_cur3, b_frag,
-                                                       acc[3], 0, 0, 0);
-      a_cur0 = a_nxt0; a_cur1 = a_nxt1; a_cur2 = a_nxt2; a_cur3 = a_nxt3;
-    }
-#undef DRLA_MH_LOAD
-  }
-  MhSide side;
-  if (SIDE == MH_MASK) mh_load_mask(side, side_src, row0, N);
-  if (SIDE == MH_BIAS) mh_load_bias(side, side_src, nout);
-  mh_epilogue<RELU, SIDE>(acc, act_out, side, dz_global, colsum, stash,
-                          dh_global, row0, N, nout);
-}
-
-// backward: takes PRE-TRANSPOSED weights (wrapper-built):
-//   wT3p [256,32] = pad(W3p^T), wT2p/wT1p/wT2v/wT1v [256,256] = W^T,
-//   W3v [1,256] as-is (value out layer backward is an outer product).
-extern "C" __global__ __launch_bounds__(256) void drla_mlp_heads_bwd(
-    const bf16raw* __restrict__ dlogits,   // [N,A]
-    const float* __restrict__ dvalue,      // [N]
-    const bf16raw* __restrict__ stash,     // [N,5*256]
-    const bf16raw* __restrict__ wT1p, const bf16raw* __restrict__ wT2p,
-    const bf16raw* __restrict__ wT3p,      // [256,32] padded
-    const bf16raw* __restrict__ wT1v, const bf16raw* __restrict__ wT2v,
-    const bf16raw* __restrict__ W3v,       // [1,256]
-    bf16raw* __restrict__ dz1p, bf16raw* __restrict__ dz2p,  // [N,256]
-    bf16raw* __restrict__ dz1v, bf16raw* __restrict__ dz2v,  // [N,256]
-    float* __restrict__ dh,                // [N,256], ZEROED (atomics)
-    float* __restrict__ db1p, float* __restrict__ db2p,
-    float* __restrict__ db3p,              // [A]
-    float* __restrict__ db1v, float* __restrict__ db2v,
-    float* __restrict__ db3v,              // [1]
-    int N, int A) {
-  // grid: (ceil(N/16), 2) — blockIdx.y 0 = policy chain, 1 = value chain;
-  // both accumulate dh atomically.
-  __shared__ bf16raw dza[MH_BM][MH_LD];
-  __shared__ bf16raw dzb[MH_BM][MH_LD];
-  __shared__ float colsum[MH_HID];
-
-  const int tid = threadIdx.x;
-  const int row0 = blockIdx.x * MH_BM;
-  const long long soff = (long long)N * MH_HID;
-  const bf16raw* a1p = stash;
-  const bf16raw* a2p = stash + soff;
-  const bf16raw* a1v = stash + 2 * soff;
-  const bf16raw* a2v = stash + 3 * soff;
-
-  if (tid < MH_HID) colsum[tid] = 0.0f;
-
-  if (blockIdx.y == 0) {
-    // ---- policy chain ----
-    {
-      const int r = tid >> 4;
-      const int c = tid & 15;
-      for (int cc = c; cc < 32; cc += 16) {
-        const int grow = row0 + r;
-        bf16raw v = 0;
-        if (cc < A && grow < N) v = dlogits[(long long)grow * A + cc];
-        dza[r][cc] = v;
-      }
-    }
-    __syncthreads();
-    if (tid < A) {
-      float s = 0.0f;
-      for (int r = 0; r < MH_BM; ++r) {
-        if (row0 + r < N) s += drla_bf16_to_f32(dza[r][tid]);
-      }
-      atomicAdd(&db3p[tid], s);
-    }
-    __syncthreads();
-    mh_pass<false, MH_MASK>(dza, dzb, wT3p, a2p, dz2p, colsum, nullptr,
-                            nullptr, row0, N, MH_HID, 32);
-    if (tid < MH_HID) {
-      atomicAdd(&db2p[tid], colsum[tid]);
-      colsum[tid] = 0.0f;
-    }
-    __syncthreads();
-    mh_pass<false, MH_MASK>(dzb, dza, wT2p, a1p, dz1p, colsum, nullptr,
-                            nullptr, row0, N, MH_HID, MH_HID);
-    if (tid < MH_HID) atomicAdd(&db1p[tid], colsum[tid]);
-    __syncthreads();
-    mh_pass<false, MH_NONE>(dza, dzb, wT1p, nullptr, nullptr, nullptr,
-                            nullptr, dh, row0, N, MH_HID, MH_HID);
-  } else {
-    // ---- value chain ----
-    // da2v[r][i] = dvalue[r] * W3v[i], masked by a2v
-    {
-      const int r = tid >> 4;
-      const int c0 = (tid & 15) * 16;
-      const int grow = row0 + r;
-      const float dv = (grow < N) ? dvalue[grow] : 0.0f;
-      for (int c = 0; c < 16; ++c) {
-        const int ic = c0 + c;
-        float v = dv * drla_bf16_to_f32(W3v[ic]);
-        if (grow < N) {
-          const float a = drla_bf16_to_f32(a2v[(long long)grow * MH_HID + ic]);
-          v = (a > 0.0f) ? v : 0.0f;
-        } else {
-          v = 0.0f;
-        }
-        const bf16raw bv = drla_f32_to_bf16(v);
-        dza[r][ic] = bv;
-        if (grow < N) dz2v[(long long)grow * MH_HID + ic] = bv;
-        atomicAdd(&colsum[ic], v);
-      }
-    }
-    __syncthreads();
-    if (tid < MH_HID) {
-      atomicAdd(&db2v[tid], colsum[tid]);
-      colsum[tid] = 0.0f;
-    }
-    if (tid == 0) {
-      float s = 0.0f;
-      for (int r = 0; r < MH_BM && row0 + r < N; ++r) s += dvalue[row0 + r];
-      atomicAdd(&db3v[0], s);
-    }
-    __syncthreads();
-    mh_pass<false, MH_MASK>(dza, dzb, wT2v, a1v, dz1v, colsum, nullptr,
-                            nullptr, row0, N, MH_HID, MH_HID);
-    if (tid < MH_HID) atomicAdd(&db1v[tid], colsum[tid]);
-    __syncthreads();
-    mh_pass<false, MH_NONE>(dzb, dza, wT1v, nullptr, nullptr, nullptr,
-                            nullptr, dh, row0, N, MH_HID, MH_HID);
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Weight-transpose pack: the dgrad kernel above wants W^T operands, which
 // the wrapper used to build with 5 .t().contiguous() copies + an F.pad —
@@ -585,165 +406,6 @@ extern "C" __global__ void drla_heads_wt_pack(
       v = w3v[i - 270336];
     }
     out[i] = v;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// All six head wgrads in ONE launch: dW = dz^T @ act with K = N rows.
-// Replaces 6 hipBLASLt GEMM dispatches (~5/step at ~13 us each, r23).
-//
-// Jobs (all outputs [M,256] bf16):
-//   0: dW1p = dz1p^T @ hb     M=256      3: dW2v = dz2v^T @ a1v  M=256
-//   1: dW2p = dz2p^T @ a1p    M=256      4: dW3p = dlogits^T @ a2p  M=A
-//   2: dW1v = dz1v^T @ hb     M=256      5: dW3v = dvalue^T @ a2v   M=1
-//
-// Both MFMA operands are k-major in global (dz[k][m], act[k][n]), so each
-// 32k-chunk is staged TRANSPOSED into padded LDS (vec8 global row loads,
-// scalar LDS writes) and the fragments read back as vec8 ds_read_b128
-// (row stride 40 elems = 80 B keeps 16 B alignment).
-#define HW_LDK 40  // 32 + 8 pad
-
-extern "C" __global__ __launch_bounds__(256) void drla_heads_wgrad(
-    const bf16raw* __restrict__ dz1p, const bf16raw* __restrict__ dz2p,
-    const bf16raw* __restrict__ dz1v, const bf16raw* __restrict__ dz2v,
-    const bf16raw* __restrict__ dlogits,  // [N,A]
-    const float* __restrict__ dvalue,     // [N]
-    const bf16raw* __restrict__ stash,    // [N,5*256]
-    bf16raw* __restrict__ dw1p, bf16raw* __restrict__ dw2p,
-    bf16raw* __restrict__ dw3p,           // [A,256]
-    bf16raw* __restrict__ dw1v, bf16raw* __restrict__ dw2v,
-    bf16raw* __restrict__ dw3v,           // [1,256]
-    const float* __restrict__ ws_tail,    // f32 bias partials from heads_bwd
-    bf16raw* __restrict__ db1p, bf16raw* __restrict__ db2p,
-    bf16raw* __restrict__ db3p, bf16raw* __restrict__ db1v,
-    bf16raw* __restrict__ db2v, bf16raw* __restrict__ db3v,
-    int N, int A) {
-  // grid.x = 73: jobs 0-3 are 4x4 tiles of 64x64 (blocks 0..63), job 4 is
-  // blocks 64..67 (one m-tile, A <= 32), job 5 blocks 68..71; block 72
-  // converts the f32 bias-grad partials to six contiguous bf16 tensors
-  // (contiguous outputs avoid AccumulateGrad's clone-a-view kernels).
-  const int bid = blockIdx.x;
-  if (bid == 72) {
-    const int tid = threadIdx.x;
-    const int total = 4 * 256 + A + 1;
-    for (int i = tid; i < total; i += 256) {
-      const bf16raw v = drla_f32_to_bf16(ws_tail[i]);
-      if (i < 256)            db1p[i] = v;
-      else if (i < 512)       db2p[i - 256] = v;
-      else if (i < 512 + A)   db3p[i - 512] = v;
-      else if (i < 768 + A)   db1v[i - 512 - A] = v;
-      else if (i < 1024 + A)  db2v[i - 768 - A] = v;
-      else                    db3v[0] = v;
-    }
-    return;
-  }
-  int job, mt, nt;
-  if (bid < 64) {
-    job = bid >> 4;
-    mt = (bid >> 2) & 3;
-    nt = bid & 3;
-  } else if (bid < 68) {
-    job = 4; mt = 0; nt = bid - 64;
-  } else {
-    job = 5; mt = 0; nt = bid - 68;
-  }
-  const long long soff = (long long)N * MH_HID;
-  const bf16raw* dz;
-  const bf16raw* act;
-  bf16raw* out;
-  int M;
-  switch (job) {
-    case 0: dz = dz1p; act = stash + 4 * soff; out = dw1p; M = 256; break;
-    case 1: dz = dz2p; act = stash;            out = dw2p; M = 256; break;
-    case 2: dz = dz1v; act = stash + 4 * soff; out = dw1v; M = 256; break;
-    case 3: dz = dz2v; act = stash + 2 * soff; out = dw2v; M = 256; break;
-    case 4: dz = dlogits; act = stash + soff;  out = dw3p; M = A;   break;
-    default: dz = nullptr; act = stash + 3 * soff; out = dw3v; M = 1;
-  }
-  const int m0 = mt * 64;
-  const int n0 = nt * 64;
-
-  __shared__ bf16raw dzT[64][HW_LDK];   // [m_local][k_local]
-  __shared__ bf16raw actT[64][HW_LDK];  // [n_local][k_local]
-
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-
-  f32x4 acc[4];
-  for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
-
-  // software-pipelined K(=N)-loop: next chunk's globals prefetch into
-  // registers during this chunk's MFMA (same pattern as the conv wgrad)
-  const int st_kk = tid >> 3;
-  const int st_c0 = (tid & 7) * 8;
-  const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  bf16x8 r_act = z8, r_dz = z8;
-
-  auto load_chunk = [&](int k0) {
-    const int k = k0 + st_kk;
-    r_act = z8;
-    if (k < N) {
-      r_act = *reinterpret_cast<const bf16x8*>(
-          act + (long long)k * MH_HID + n0 + st_c0);
-    }
-    if (job < 4) {           // dz [N,256] bf16, vec8
-      r_dz = z8;
-      if (k < N) {
-        r_dz = *reinterpret_cast<const bf16x8*>(
-            dz + (long long)k * MH_HID + m0 + st_c0);
-      }
-    } else if (job == 4) {   // dlogits [N,A], scalar predicated
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int m = st_c0 + e;
-        r_dz[e] = (k < N && m < A)
-            ? (short)dlogits[(long long)k * A + m] : (short)0;
-      }
-    } else {                 // dvalue [N] f32, M = 1
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int m = st_c0 + e;
-        r_dz[e] = (k < N && m == 0)
-            ? (short)drla_f32_to_bf16(dvalue[k]) : (short)0;
-      }
-    }
-  };
-
-  auto store_chunk = [&]() {
-    actT[st_c0 + 0][st_kk] = r_act[0]; actT[st_c0 + 1][st_kk] = r_act[1];
-    actT[st_c0 + 2][st_kk] = r_act[2]; actT[st_c0 + 3][st_kk] = r_act[3];
-    actT[st_c0 + 4][st_kk] = r_act[4]; actT[st_c0 + 5][st_kk] = r_act[5];
-    actT[st_c0 + 6][st_kk] = r_act[6]; actT[st_c0 + 7][st_kk] = r_act[7];
-    dzT[st_c0 + 0][st_kk] = r_dz[0]; dzT[st_c0 + 1][st_kk] = r_dz[1];
-    dzT[st_c0 + 2][st_kk] = r_dz[2]; dzT[st_c0 + 3][st_kk] = r_dz[3];
-    dzT[st_c0 + 4][st_kk] = r_dz[4]; dzT[st_c0 + 5][st_kk] = r_dz[5];
-    dzT[st_c0 + 6][st_kk] = r_dz[6]; dzT[st_c0 + 7][st_kk] = r_dz[7];
-  };
-
-  load_chunk(0);
-  for (int k0 = 0; k0 < N; k0 += 32) {
-    store_chunk();
-    __syncthreads();
-    if (k0 + 32 < N) load_chunk(k0 + 32);
-    // wave w: m rows [w*16, w*16+16); frags vec8 from LDS
-    const bf16x8 a_frag = *reinterpret_cast<const bf16x8*>(
-        &dzT[wave * 16 + (lane & 15)][(lane >> 4) * 8]);
-    for (int ni = 0; ni < 4; ++ni) {
-      const bf16x8 b_frag = *reinterpret_cast<const bf16x8*>(
-          &actT[ni * 16 + (lane & 15)][(lane >> 4) * 8]);
-      acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          a_frag, b_frag, acc[ni], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  // D: lane l reg r -> row (l>>4)*4+r (m), col l&15 (n)
-  for (int ni = 0; ni < 4; ++ni) {
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + wave * 16 + (lane >> 4) * 4 + r;
-      const int n = n0 + ni * 16 + (lane & 15);
-      if (m < M) out[(long long)m * MH_HID + n] = drla_f32_to_bf16(acc[ni][r]);
-    }
   }
 }
 
