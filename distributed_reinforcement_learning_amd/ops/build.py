@@ -36,6 +36,7 @@ SOURCES = [
     "gate_gemm.hip",
     "dueling_q.hip",
     "r2d2_head.hip",
+    "lstm_proj.hip",
     "per_tree.hip",
     "dqn_loss.hip",
     "a2c_loss.hip",

@@ -2100,6 +2100,165 @@ std::vector<torch::Tensor> r2d2_head_bwd(
   return {dh, dwt, dbt, dwo, dbo};
 }
 
+// ---- R2D2 LSTM projection (lstm_proj.hip) -----------------------------------
+// conv [M, F1], emb [M, F2], dxg [M, 4H]: 2-D bf16, unit column stride, rows
+// at multiples of 16 bytes, read in place with their row stride. weight is
+// lstm.weight [F1 + F2 + H, 4H] whole.
+struct LpOperand { const bf16raw* p; long long ld; };
+LpOperand lp_operand(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2, name, " must be a 2-D GPU tensor");
+  const bf16raw* p = bf16_ptr(t, name);
+  const int64_t rows = t.size(0), cols = t.size(1);
+  TORCH_CHECK(cols >= 8 && cols % 8 == 0, name,
+              ": the column count must be a positive multiple of 8");
+  TORCH_CHECK(rows < (int64_t(1) << 30) && cols < (int64_t(1) << 30), name,
+              ": too large for the LSTM projection kernels");
+  const int64_t ld = rows > 1 ? t.stride(0) : cols;
+  TORCH_CHECK(t.stride(1) == 1 && ld >= cols, name,
+              " must have unit column stride and non-overlapping rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 8 == 0, name,
+              ": every row must start at a multiple of 16 bytes");
+  return {p, ld};
+}
+// the shapes of one layer: conv [M, F1], emb [M, F2], weight [F1 + F2 + H, 4H]
+struct LpShape { int64_t M, F1, F2, H, N; };
+LpShape lp_shape(const torch::Tensor& conv, const torch::Tensor& emb,
+                 const torch::Tensor& weight) {
+  TORCH_CHECK(weight.dim() == 2 && conv.dim() == 2 && emb.dim() == 2,
+              "LSTM projection: conv, emb and weight must be 2-D");
+  const int64_t M = conv.size(0), F1 = conv.size(1), F2 = emb.size(1);
+  const int64_t N = weight.size(1), H = N / 4;
+  TORCH_CHECK(emb.size(0) == M, "conv and emb must have the same rows");
+  TORCH_CHECK(F1 >= 64 && F1 % 64 == 0,
+              "the conv width F1 must be a positive multiple of 64, got ", F1);
+  TORCH_CHECK(N == 4 * H && H % 2 == 0 && H >= 2 && H <= LSTM_SEQ_MAX_HIDDEN,
+              "weight must be [F + H, 4H] with H even, 2 <= H <= ",
+              LSTM_SEQ_MAX_HIDDEN, ", got ", N, " columns");
+  TORCH_CHECK(weight.size(0) == F1 + F2 + H,
+              "weight must have F1 + F2 + H = ", F1 + F2 + H, " rows, got ",
+              weight.size(0));
+  TORCH_CHECK(M * N < (int64_t(1) << 31),
+              "too many rows for the LSTM projection kernels");
+  return {M, F1, F2, H, N};
+}
+
+// forward split-K: enough splits to put about two blocks on each of the 256
+// CUs, each split keeping at least DRLA_LP_SPLIT_CHUNKS 64-k chunks, and at
+// least three splits where the chunks allow it: one block per tile leaves the
+// 53-chunk serial chain of the shipped width exposed even with every CU busy
+// (sweep table in profiles/lstm_proj_r14.md)
+constexpr int DRLA_LP_SPLIT_CHUNKS = 6;
+int lstm_proj_split(int64_t M, int64_t F, int64_t N) {
+  TORCH_CHECK(M >= 0 && F >= 8 && N >= 8, "LSTM projection: bad shape");
+  const int64_t tiles = ((N + DRLA_LP_TILE - 1) / DRLA_LP_TILE) *
+                        ((std::max<int64_t>(M, 1) + DRLA_LP_TILE - 1) /
+                         DRLA_LP_TILE);
+  const int64_t chunks = (F + DRLA_LP_TILE - 1) / DRLA_LP_TILE;
+  const int64_t cap = chunks / DRLA_LP_SPLIT_CHUNKS;
+  const int64_t s = std::max<int64_t>(std::min<int64_t>(512 / tiles, cap),
+                                      std::min<int64_t>(3, cap));
+  return (int)std::clamp<int64_t>(s, 1, DRLA_LP_MAX_SPLIT);
+}
+
+// xg [M, 4H] = bf16(conv @ W[:F1] + emb @ W[F1:F] + bias); split = 0:
+// lstm_proj_split
+torch::Tensor lstm_proj_fwd(const torch::Tensor& conv,
+                            const torch::Tensor& emb,
+                            const torch::Tensor& weight,
+                            const torch::Tensor& bias, int64_t split) {
+  const LpOperand a = lp_operand(conv, "conv"), e = lp_operand(emb, "emb"),
+                  w = lp_operand(weight, "weight");
+  const LpShape s = lp_shape(conv, emb, weight);
+  TORCH_CHECK(bias.is_cuda() && bias.dim() == 1 && bias.size(0) == s.N &&
+                  bias.stride(0) == 1,
+              "bias must be a dense [4H] GPU tensor");
+  const bf16raw* bp = BF16P(bias);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(bp) % 16 == 0,
+              "bias must start at a multiple of 16 bytes");
+  TORCH_CHECK(split >= 0 && split <= DRLA_LP_MAX_SPLIT, "split out of range");
+  auto xg = torch::empty({s.M, s.N}, conv.options());
+  if (s.M == 0) return xg;
+  const int S = split > 0 ? (int)split
+                          : lstm_proj_split(s.M, s.F1 + s.F2, s.N);
+  auto ws = torch::empty({S, s.M, s.N}, conv.options().dtype(torch::kFloat));
+  hipLaunchKernelGGL(
+      drla_lstm_proj_fwd,
+      dim3((s.N + DRLA_LP_TILE - 1) / DRLA_LP_TILE,
+           (s.M + DRLA_LP_TILE - 1) / DRLA_LP_TILE, S),
+      dim3(DRLA_LP_BLOCK), 0, cur_stream(), a.p, a.ld, e.p, e.ld, w.p, w.ld,
+      ws.data_ptr<float>(), (int)s.M, (int)s.F1, (int)s.F2, (int)s.N);
+  const long long n4 = s.M * s.N / 4;
+  hipLaunchKernelGGL(drla_lstm_proj_reduce, dim3(drla_grid(n4)),
+                     dim3(DRLA_LP_BLOCK), 0, cur_stream(),
+                     static_cast<const float*>(ws.data_ptr<float>()), bp,
+                     BF16PM(xg), n4, (int)s.N, S);
+  return xg;
+}
+
+// [dconv [M, F1], demb [M, F2]] = dxg [M, 4H] @ W[:F]^T
+std::vector<torch::Tensor> lstm_proj_dgrad(const torch::Tensor& dxg,
+                                           const torch::Tensor& weight,
+                                           int64_t F1, int64_t F2) {
+  const LpOperand d = lp_operand(dxg, "dxg"), w = lp_operand(weight, "weight");
+  const int64_t M = dxg.size(0), N = dxg.size(1), H = N / 4;
+  TORCH_CHECK(F1 >= 64 && F1 % 64 == 0,
+              "the conv width F1 must be a positive multiple of 64, got ", F1);
+  TORCH_CHECK(F2 >= 8 && F2 % 8 == 0,
+              "the emb width F2 must be a positive multiple of 8, got ", F2);
+  TORCH_CHECK(N == 4 * H && H % 2 == 0 && H >= 2 && H <= LSTM_SEQ_MAX_HIDDEN,
+              "dxg must be [M, 4H] with H even, 2 <= H <= ",
+              LSTM_SEQ_MAX_HIDDEN);
+  TORCH_CHECK(weight.size(1) == N && weight.size(0) == F1 + F2 + H,
+              "weight must be [F1 + F2 + H, 4H]");
+  auto dconv = torch::empty({M, F1}, dxg.options());
+  auto demb = torch::empty({M, F2}, dxg.options());
+  if (M == 0) return {dconv, demb};
+  hipLaunchKernelGGL(
+      drla_lstm_proj_dgrad,
+      dim3(F1 / DRLA_LP_TILE + (F2 + DRLA_LP_TILE - 1) / DRLA_LP_TILE,
+           (M + DRLA_LP_TILE - 1) / DRLA_LP_TILE),
+      dim3(DRLA_LP_BLOCK), 0, cur_stream(), d.p, d.ld, w.p, w.ld,
+      BF16PM(dconv), BF16PM(demb), (int)M, (int)F1, (int)F2, (int)N);
+  return {dconv, demb};
+}
+
+// [dW [F + H, 4H], db [4H]] from conv, emb, the h_prev [M, H] stash of
+// lstm_seq_train_fwd and dxg [M, 4H]
+std::vector<torch::Tensor> lstm_proj_wgrad(const torch::Tensor& conv,
+                                           const torch::Tensor& emb,
+                                           const torch::Tensor& h_prev,
+                                           const torch::Tensor& dxg) {
+  const LpOperand a = lp_operand(conv, "conv"), e = lp_operand(emb, "emb"),
+                  d = lp_operand(dxg, "dxg");
+  const int64_t M = conv.size(0), F1 = conv.size(1), F2 = emb.size(1);
+  const int64_t N = dxg.size(1), H = N / 4;
+  TORCH_CHECK(F1 % 64 == 0,
+              "the conv width F1 must be a positive multiple of 64, got ", F1);
+  TORCH_CHECK(N == 4 * H && H % 2 == 0 && H >= 2 && H <= LSTM_SEQ_MAX_HIDDEN,
+              "dxg must be [M, 4H] with H even, 2 <= H <= ",
+              LSTM_SEQ_MAX_HIDDEN);
+  TORCH_CHECK(emb.size(0) == M && dxg.size(0) == M,
+              "conv, emb and dxg must have the same rows");
+  TORCH_CHECK(h_prev.is_cuda() && h_prev.dim() == 2 && h_prev.size(0) == M &&
+                  h_prev.size(1) == H && h_prev.is_contiguous(),
+              "h_prev must be a contiguous [M, H] GPU tensor");
+  const int64_t R = F1 + F2 + H;
+  if (M == 0) {
+    return {torch::zeros({R, N}, conv.options()),
+            torch::zeros({N}, conv.options())};
+  }
+  auto dw = torch::empty({R, N}, conv.options());
+  auto db = torch::empty({N}, conv.options());
+  hipLaunchKernelGGL(
+      drla_lstm_proj_wgrad,
+      dim3(((R + DRLA_LP_TILE - 1) / DRLA_LP_TILE) *
+           ((N + DRLA_LP_TILE - 1) / DRLA_LP_TILE)),
+      dim3(DRLA_LP_BLOCK), 0, cur_stream(), a.p, a.ld, e.p, e.ld,
+      BF16P(h_prev), d.p, d.ld, BF16PM(dw), BF16PM(db), (int)M, (int)F1,
+      (int)F2, (int)H, (int)N);
+  return {dw, db};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2193,6 +2352,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "R2D2 dueling head backward -> [dh, dWt, dbt, dWo, dbo]",
         py::arg("dq"), py::arg("h"), py::arg("z"), py::arg("wt"),
         py::arg("wo"));
+  // underscore: reached through ops/lstm_proj_op.py only
+  m.def("_lstm_proj_fwd", &lstm_proj_fwd,
+        "conv @ W[:F1] + emb @ W[F1:F] + bias -> xg [M, 4H]",
+        py::arg("conv"), py::arg("emb"), py::arg("weight"), py::arg("bias"),
+        py::arg("split") = 0);
+  m.def("_lstm_proj_dgrad", &lstm_proj_dgrad,
+        "dxg @ W[:F]^T -> [dconv, demb]", py::arg("dxg"), py::arg("weight"),
+        py::arg("F1"), py::arg("F2"));
+  m.def("_lstm_proj_wgrad", &lstm_proj_wgrad,
+        "[conv | emb | h_prev]^T @ dxg -> [dW, db]", py::arg("conv"),
+        py::arg("emb"), py::arg("h_prev"), py::arg("dxg"));
+  m.def("_lstm_proj_split", &lstm_proj_split,
+        "K-split of the LSTM projection forward for a shape", py::arg("M"),
+        py::arg("F"), py::arg("N"));
   m.def("dqn_loss_fwd", &dqn_loss_fwd,
         "fused double-DQN target + IS-weighted TD loss (K8)");
   m.def("dqn_loss_bwd", &dqn_loss_bwd, "closed-form K8 backward");

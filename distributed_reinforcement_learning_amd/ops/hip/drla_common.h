@@ -139,6 +139,13 @@ struct DrlaDqGrads {
 #define DRLA_R2H_BM 16
 #define DRLA_R2H_BLOCK 256
 
+// R2D2 LSTM projection (lstm_proj.hip): DRLA_LP_BLOCK threads per 64 x 64
+// output tile, the contraction in chunks of DRLA_LP_TILE; the forward's grid.z
+// is its K-split, at most DRLA_LP_MAX_SPLIT
+#define DRLA_LP_BLOCK 256
+#define DRLA_LP_TILE 64
+#define DRLA_LP_MAX_SPLIT 16
+
 // fused V-trace loss: T sizes the LDS scan buffers, A is the softmax width
 #define VT_MAX_T 128
 #define VT_MAX_A 64

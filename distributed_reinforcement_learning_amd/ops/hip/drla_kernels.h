@@ -226,6 +226,24 @@ DRLA_KERNEL drla_r2h_wgrad(const float*, const bf16raw*, const bf16raw*,
                            const bf16raw*, bf16raw*, bf16raw*, bf16raw*,
                            bf16raw*, int, int, int);
 
+// ---- lstm_proj.hip (R2D2 LSTM input projection; row strides in elements) ---
+// fwd: conv, ldc, emb, lde, w, ldw, workspace [S][M][N], M, F1, F2, N
+DRLA_KERNEL drla_lstm_proj_fwd(const bf16raw*, long long, const bf16raw*,
+                               long long, const bf16raw*, long long, float*,
+                               int, int, int, int);
+// reduce: workspace, bias, xg, M*N/4, N, S
+DRLA_KERNEL drla_lstm_proj_reduce(const float*, const bf16raw*, bf16raw*,
+                                  long long, int, int);
+// dgrad: dxg, lddg, w, ldw, dconv, demb, M, F1, F2, N
+DRLA_KERNEL drla_lstm_proj_dgrad(const bf16raw*, long long, const bf16raw*,
+                                 long long, bf16raw*, bf16raw*, int, int, int,
+                                 int);
+// wgrad: conv, ldc, emb, lde, h_prev, dxg, lddg, dw, db, M, F1, F2, H, N
+DRLA_KERNEL drla_lstm_proj_wgrad(const bf16raw*, long long, const bf16raw*,
+                                 long long, const bf16raw*, const bf16raw*,
+                                 long long, bf16raw*, bf16raw*, int, int, int,
+                                 int, int);
+
 // ---- per_tree.hip ---------------------------------------------------------
 DRLA_KERNEL drla_per_update(float*, const long long*, const float*, int,
                             long long);
