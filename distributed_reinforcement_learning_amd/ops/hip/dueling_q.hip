@@ -38,90 +38,26 @@
 // slice requested before first use; the activation is the 16-byte LDS read.
 // A lane then holds four consecutive outputs of one row: one 8-byte store.
 //
-// Packed-f32 VALU ops stay out of this file as in maxpool.hip: every function
-// carries DQ_FN, helpers are this file's own or always-inline builtins.
+// Packed-f32 VALU ops stay out of this file: every function carries NOPK_FN,
+// helpers are drla_nopk.h's (which says why), this file's own or builtins.
 
 #include "drla_kernels.h"
-#include "conv_wgrad_lds.h"
-
-#define DQ_FN __attribute__((target("no-packed-fp32-ops")))
-#define DQ_INL DQ_FN __device__ __forceinline__
-#define DQ_PRE(threads) extern "C" DQ_FN __launch_bounds__(threads)
+#include "drla_nopk.h"
 
 namespace {
 
 constexpr int DQ_H = DRLA_DQ_HID;
-constexpr int DQ_BK = 64;
-constexpr int DQ_PITCH = (DQ_BK + 8) * 2;  // bytes per k-contiguous LDS row
-constexpr int DQ_KC_SUB = 64 * DQ_PITCH;   // one k-contiguous 64-row tile
-constexpr int DQ_KR_ROWB = 128;            // k-rows image: 64 columns
-constexpr int DQ_KR_SUB = DRLA_WG_ROWS * DQ_KR_ROWB;
-constexpr int DQ_SUB = DQ_KC_SUB > DQ_KR_SUB ? DQ_KC_SUB : DQ_KR_SUB;
 constexpr int DQ_ACT_LD = DQ_H + 8;        // tail activation rows, elements
-static_assert(DQ_BK == DRLA_WG_ROWS && DRLA_DQ_BLOCK == 256,
-              "the k-rows image of conv_wgrad_lds.h is 64 k x 64 columns, "
-              "staged by 256 threads in two passes");
-static_assert((DQ_PITCH / 16) % 2 == 1 && (DQ_ACT_LD * 2 / 16) % 2 == 1,
+static_assert(DRLA_DQ_BLOCK == 256,
+              "the tiles of drla_nopk.h are staged by 256 threads in two "
+              "passes");
+static_assert((DQ_ACT_LD * 2 / 16) % 2 == 1,
               "odd pitch in 16-byte units: fragment reads spread over banks");
 static_assert(DRLA_DQ_TAIL_BLOCK == 2 * 4 * 64 && DQ_H == 4 * 64,
               "tail: two branches x four waves x 64 output columns");
 static_assert(DRLA_DQ_MAX_A == 32 && DRLA_DQ_BM == 16,
               "layer 3 is one 32-deep k-step backward, two 16-row tiles "
               "forward");
-
-typedef __attribute__((ext_vector_type(2))) float dq_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 dq_bf16x2;
-typedef __attribute__((ext_vector_type(4))) short dq_s16x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int dq_u32x2;
-
-DQ_INL void dq_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-DQ_INL int dq_min(int a, int b) { return a < b ? a : b; }
-DQ_INL float dq_f32(bf16raw u) {
-  return __builtin_bit_cast(float, (unsigned int)u << 16);
-}
-// two f32 -> packed bf16, round to nearest even: one v_cvt_pk_bf16_f32
-DQ_INL unsigned int dq_round2(float a, float b) {
-  return __builtin_bit_cast(
-      unsigned int, __builtin_convertvector(dq_f32x2{a, b}, dq_bf16x2));
-}
-DQ_INL dq_u32x2 dq_round4(f32x4 v) {
-  return dq_u32x2{dq_round2(v[0], v[1]), dq_round2(v[2], v[3])};
-}
-DQ_INL bf16raw dq_round1(float a) {
-  return (bf16raw)(dq_round2(a, a) & 0xffffu);
-}
-DQ_INL float dq_relu(float v) { return v > 0.f ? v : 0.f; }
-// a bf16 value is > 0 iff its bits, read as a signed short, are
-DQ_INL bool dq_pos(bf16raw u) { return (short)u > 0; }
-
-// drla_wg_chunk_off<128> / drla_wg_tr_off<128> at run time, restated under
-// DQ_FN (the header's functions are not always_inline) and held equal to
-// them for every argument at compile time
-DQ_INL constexpr int dq_kr_chunk_off(int row, int ch) {
-  const int sw = (row & 1) | (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2);
-  return DQ_KR_ROWB * row + 16 * (ch ^ sw);
-}
-DQ_INL constexpr int dq_kr_tr_off(int lane, int tile) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  return dq_kr_chunk_off(8 * g + q, 2 * tile + (p >> 1)) + 8 * (p & 1);
-}
-constexpr bool dq_kr_maps_match_header() {
-  for (int row = 0; row < DRLA_WG_ROWS; ++row)
-    for (int ch = 0; ch < 8; ++ch)
-      if (dq_kr_chunk_off(row, ch) != drla_wg_chunk_off<DQ_KR_ROWB>(row, ch))
-        return false;
-  for (int lane = 0; lane < 64; ++lane)
-    for (int tile = 0; tile < 4; ++tile)
-      if (dq_kr_tr_off(lane, tile) != drla_wg_tr_off<DQ_KR_ROWB>(lane, tile))
-        return false;
-  return true;
-}
-static_assert(dq_kr_maps_match_header(),
-              "the k-rows maps are those conv_wgrad_lds.h proves");
 
 // ---- the tiled product ----------------------------------------------------
 
@@ -147,7 +83,7 @@ struct DqTile {
 
   // tile0: first row (k-contiguous) / column (k-rows) of the tile; nmax: how
   // many the matrix has (k-rows: a multiple of 8)
-  DQ_INL void init(const DqOperand& g_, int tile0, int nmax, int tid) {
+  NOPK_INL void init(const DqOperand& g_, int tile0, int nmax, int tid) {
     g = g_;
     srow = tid >> 3;
     sch = tid & 7;
@@ -157,21 +93,21 @@ struct DqTile {
       if constexpr (KROWS) {
         const int c = tile0 + 8 * sch;
         live |= (unsigned int)(c < nmax) << j;
-        off[j] = dq_min(c, nmax - 8);
+        off[j] = nopk_min(c, nmax - 8);
       } else {
         const int row = tile0 + srow + 32 * j;
         live |= (unsigned int)(row < nmax) << j;
-        off[j] = (long long)dq_min(row, nmax - 1) * g.ld;
+        off[j] = (long long)nopk_min(row, nmax - 1) * g.ld;
       }
     }
   }
 
   // global -> registers for the chunk at k0 of a range that ends at k_end
-  DQ_INL void load(int k0, int k_end) {
+  NOPK_INL void load(int k0, int k_end) {
     const bool second = k0 >= g.kseg;
     const bf16raw* p = second ? g.p1 : g.p0;
     const int kb = k0 - (second ? g.kseg : 0);
-    const int ke = dq_min(k_end - (second ? g.kseg : 0), g.kseg);
+    const int ke = nopk_min(k_end - (second ? g.kseg : 0), g.kseg);
     klive = 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -179,44 +115,35 @@ struct DqTile {
       if constexpr (KROWS) {
         const int k = kb + srow + 32 * j;
         klive |= (unsigned int)(k < ke) << j;
-        koff = (long long)dq_min(k, g.kseg - 1) * g.ld;
+        koff = (long long)nopk_min(k, g.kseg - 1) * g.ld;
       } else {
         const int k = kb + 8 * sch;
         klive |= (unsigned int)(k < ke) << j;
-        koff = dq_min(k, g.kseg - 8);
+        koff = nopk_min(k, g.kseg - 8);
       }
       r[j] = *reinterpret_cast<const bf16x8*>(p + off[j] + koff);
     }
   }
 
   // registers -> LDS image; pieces outside the matrix or the range are zeros
-  DQ_INL void store(unsigned char* lds) const {
-    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  NOPK_INL void store(unsigned char* lds) const {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const bool in = ((live >> j) & (klive >> j) & 1u) != 0;
-      const int o = KROWS ? dq_kr_chunk_off(srow + 32 * j, sch)
-                          : (srow + 32 * j) * DQ_PITCH + 16 * sch;
-      *reinterpret_cast<bf16x8*>(lds + o) = in ? r[j] : z;
+      const int o = KROWS ? nopk_chunk_off(srow + 32 * j, sch)
+                          : (srow + 32 * j) * NOPK_PITCH + 16 * sch;
+      *reinterpret_cast<bf16x8*>(lds + o) = in ? r[j] : nopk_zero8();
     }
   }
 
   // 16x16x32 operand of 16-wide tile t16, k-step ks: lane l gets element
   // (t16 * 16 + l % 16, 32 ks + 8 (l / 16) + e) in e = 0..7. EXEC is full.
-  static DQ_INL bf16x8 frag(const unsigned char* lds, int t16, int ks,
+  static NOPK_INL bf16x8 frag(const unsigned char* lds, int t16, int ks,
                             int lane) {
     if constexpr (KROWS) {
-      typedef __attribute__((address_space(3))) dq_s16x4* lds_ptr;
-      const unsigned char* q =
-          lds + dq_kr_tr_off(lane, t16) + 32 * ks * DQ_KR_ROWB;
-      const dq_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)q);
-      const dq_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (lds_ptr)(q + 4 * DQ_KR_ROWB));
-      return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      return nopk_frag_kr(lds, t16, ks, lane);
     } else {
-      return *reinterpret_cast<const bf16x8*>(
-          lds + (t16 * 16 + (lane & 15)) * DQ_PITCH + 64 * ks +
-          16 * (lane >> 4));
+      return nopk_frag_kc(lds, NOPK_PITCH, t16, ks, lane);
     }
   }
 };
@@ -225,19 +152,19 @@ struct DqTile {
 // k_begin a multiple of 64. The calling wave's 16 rows are m0 + 16 wave +
 // l % 16; acc[ni][e] is column n0 + 16 ni + 4 (l / 16) + e. Rows at or past
 // mmax and columns at or past nmax contribute zeros. Every thread of the
-// block calls it with the same arguments. lds: [2][2][DQ_SUB].
+// block calls it with the same arguments. lds: [2][2][NOPK_SUB].
 template <bool A_KROWS, bool B_KROWS>
-DQ_INL void dq_product(f32x4 (&acc)[4], unsigned char* lds,
+NOPK_INL void dq_product(f32x4 (&acc)[4], unsigned char* lds,
                        const DqOperand& a, int m0, int mmax,
                        const DqOperand& b, int n0, int nmax, int k_begin,
                        int k_end) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   unsigned char* As = lds;
-  unsigned char* Bs = lds + 2 * DQ_SUB;
+  unsigned char* Bs = lds + 2 * NOPK_SUB;
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
-  const int nchunks = k_end > k_begin ? (k_end - k_begin + DQ_BK - 1) / DQ_BK
+  const int nchunks = k_end > k_begin ? (k_end - k_begin + NOPK_BK - 1) / NOPK_BK
                                       : 0;
   if (nchunks == 0) return;
 
@@ -249,38 +176,38 @@ DQ_INL void dq_product(f32x4 (&acc)[4], unsigned char* lds,
   tb.load(k_begin, k_end);
   ta.store(As);
   tb.store(Bs);
-  ta.load(k_begin + DQ_BK, k_end);
-  tb.load(k_begin + DQ_BK, k_end);
-  dq_barrier();
+  ta.load(k_begin + NOPK_BK, k_end);
+  tb.load(k_begin + NOPK_BK, k_end);
+  nopk_barrier();
 #pragma unroll 1
   for (int t = 0; t < nchunks; ++t) {
     const int cur = t & 1;
     if (t + 1 < nchunks) {
-      ta.store(As + (1 - cur) * DQ_SUB);
-      tb.store(Bs + (1 - cur) * DQ_SUB);
-      ta.load(k_begin + (t + 2) * DQ_BK, k_end);
-      tb.load(k_begin + (t + 2) * DQ_BK, k_end);
+      ta.store(As + (1 - cur) * NOPK_SUB);
+      tb.store(Bs + (1 - cur) * NOPK_SUB);
+      ta.load(k_begin + (t + 2) * NOPK_BK, k_end);
+      tb.load(k_begin + (t + 2) * NOPK_BK, k_end);
     }
 #pragma unroll
-    for (int ks = 0; ks < DQ_BK / 32; ++ks) {
+    for (int ks = 0; ks < NOPK_BK / 32; ++ks) {
       const bf16x8 af =
-          DqTile<A_KROWS>::frag(As + cur * DQ_SUB, wave, ks, lane);
+          DqTile<A_KROWS>::frag(As + cur * NOPK_SUB, wave, ks, lane);
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const bf16x8 bf =
-            DqTile<B_KROWS>::frag(Bs + cur * DQ_SUB, ni, ks, lane);
+            DqTile<B_KROWS>::frag(Bs + cur * NOPK_SUB, ni, ks, lane);
         // B first: D[n][m], a lane holds n = 4 (l / 16) .. + 3 of m = l % 16
         acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf, af, acc[ni], 0,
                                                           0, 0);
       }
     }
-    dq_barrier();
+    nopk_barrier();
   }
 }
 
 // bf16 store of a wave's 16 x 64 slice of a tile to c (row stride ldc); rows
 // < mmax and columns < nmax (a multiple of 8) only
-DQ_INL void dq_store_tile(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
+NOPK_INL void dq_store_tile(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
                           long long ldc, int m0, int mmax, int n0, int nmax) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = m0 + wave * 16 + (lane & 15);
@@ -288,8 +215,8 @@ DQ_INL void dq_store_tile(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
   for (int ni = 0; ni < 4; ++ni) {
     const int n = n0 + ni * 16 + (lane >> 4) * 4;
     if (m < mmax && n < nmax) {
-      *reinterpret_cast<dq_u32x2*>(c + (long long)m * ldc + n) =
-          dq_round4(acc[ni]);
+      *reinterpret_cast<nopk_u32x2*>(c + (long long)m * ldc + n) =
+          nopk_round4(acc[ni]);
     }
   }
 }
@@ -301,7 +228,7 @@ DQ_INL void dq_store_tile(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
 struct DqW256 {
   bf16x8 a[DQ_H / 32][4];
 };
-DQ_INL void dq_load_w256(DqW256& f, const bf16raw* __restrict__ w, int out0,
+NOPK_INL void dq_load_w256(DqW256& f, const bf16raw* __restrict__ w, int out0,
                          int lane) {
 #pragma unroll
   for (int kc = 0; kc < DQ_H / 32; ++kc) {
@@ -315,7 +242,7 @@ DQ_INL void dq_load_w256(DqW256& f, const bf16raw* __restrict__ w, int out0,
 }
 // acc[ni] = D[out0 + 16 ni + 4 (l / 16) + e][row l % 16] over the 256 k of
 // act [16][DQ_ACT_LD]
-DQ_INL void dq_mma256(f32x4 (&acc)[4], const DqW256& f,
+NOPK_INL void dq_mma256(f32x4 (&acc)[4], const DqW256& f,
                       const bf16raw (*act)[DQ_ACT_LD], int lane) {
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
@@ -332,7 +259,7 @@ DQ_INL void dq_mma256(f32x4 (&acc)[4], const DqW256& f,
 }
 // the four values a lane's acc[ni] goes with, of a [rows][256] bf16 matrix
 // row (bias: row 0) - one 8-byte load per ni
-DQ_INL void dq_load_side(ushort4v (&s)[4], const bf16raw* __restrict__ row,
+NOPK_INL void dq_load_side(ushort4v (&s)[4], const bf16raw* __restrict__ row,
                          int out0, int lane) {
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
@@ -348,13 +275,13 @@ DQ_INL void dq_load_side(ushort4v (&s)[4], const bf16raw* __restrict__ row,
 // grid (8, ceil(N / 64), S). feat [N][K] (row stride ldf), w1v / w1m [256][K]
 // -> ws [S][N][512] f32. w2t != null: also w2t [2][256][256] = W2{v,m}^T and
 // w3t [256][32] = W3v^T, columns >= A zero, every block its share.
-DQ_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_l1_fwd(
+NOPK_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_l1_fwd(
     const bf16raw* __restrict__ feat, long long ldf,
     const bf16raw* __restrict__ w1v, const bf16raw* __restrict__ w1m,
     float* __restrict__ ws, int N, int K, const bf16raw* __restrict__ w2v,
     const bf16raw* __restrict__ w2m, const bf16raw* __restrict__ w3v, int A,
     bf16raw* __restrict__ w2t, bf16raw* __restrict__ w3t) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * DQ_SUB];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * NOPK_SUB];
   const int tid = threadIdx.x;
 
   if (w2t) {
@@ -379,10 +306,10 @@ DQ_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_l1_fwd(
   }
 
   // the split's k range, in whole chunks; an empty one stores zeros
-  const int chunks = (K + DQ_BK - 1) / DQ_BK;
+  const int chunks = (K + NOPK_BK - 1) / NOPK_BK;
   const int per = (chunks + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int k_begin = dq_min((int)blockIdx.z * per, chunks) * DQ_BK;
-  const int k_end = dq_min(k_begin + per * DQ_BK, K);
+  const int k_begin = nopk_min((int)blockIdx.z * per, chunks) * NOPK_BK;
+  const int k_end = nopk_min(k_begin + per * NOPK_BK, K);
   const int m0 = blockIdx.y * 64;
   const int n0 = blockIdx.x * 64;  // column of [W1v ; W1m]
   const bf16raw* w1 = n0 < DQ_H ? w1v : w1m;
@@ -405,7 +332,7 @@ DQ_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_l1_fwd(
 
 // grid ceil(N / 16). ws [S][N][512] -> q [N][A]; z1s != null: also z1s, z2s
 // [2][G][256], rows < G.
-DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
+NOPK_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
     const float* __restrict__ ws, int S, const bf16raw* __restrict__ b1v,
     const bf16raw* __restrict__ b1m, const bf16raw* __restrict__ w2v,
     const bf16raw* __restrict__ b2v, const bf16raw* __restrict__ w2m,
@@ -437,7 +364,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
   bf16raw bias3[4];
   if (l3) {
     const int a = wq * 16 + (lane & 15);
-    const bf16raw* w3 = (c ? w3m : w3v) + dq_min(a, n3 - 1) * DQ_H;
+    const bf16raw* w3 = (c ? w3m : w3v) + nopk_min(a, n3 - 1) * DQ_H;
     const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int kc = 0; kc < DQ_H / 32; ++kc) {
@@ -448,7 +375,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       bias3[e] =
-          (c ? b3m : b3v)[dq_min(wq * 16 + (lane >> 4) * 4 + e, n3 - 1)];
+          (c ? b3m : b3v)[nopk_min(wq * 16 + (lane >> 4) * 4 + e, n3 - 1)];
     }
   }
 
@@ -457,7 +384,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
   {
     const int row = tid >> 5, col0 = (tid & 31) * 16;
     const int cc = col0 >> 8, cl = col0 & (DQ_H - 1);
-    const int grow = dq_min(row0 + row, N - 1);
+    const int grow = nopk_min(row0 + row, N - 1);
     const bf16raw* b1 = (cc ? b1m : b1v) + cl;
     const bf16x8 blo = *reinterpret_cast<const bf16x8*>(b1);
     const bf16x8 bhi = *reinterpret_cast<const bf16x8*>(b1 + 8);
@@ -487,7 +414,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
         }
       }
     }
-    dq_u32x2 o[4];
+    nopk_u32x2 o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       f32x4 v;
@@ -495,9 +422,9 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
       for (int e = 0; e < 4; ++e) {
         const int i = 4 * j + e;
         const bf16raw b = (bf16raw)(i < 8 ? blo[i & 7] : bhi[i & 7]);
-        v[e] = dq_relu(sum[j][e] + dq_f32(b));
+        v[e] = nopk_relu(sum[j][e] + nopk_f32(b));
       }
-      o[j] = dq_round4(v);
+      o[j] = nopk_round4(v);
     }
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
     const u32x4 lo = {o[0][0], o[0][1], o[1][0], o[1][1]};
@@ -510,7 +437,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
       *reinterpret_cast<u32x4*>(d + 8) = hi;
     }
   }
-  dq_barrier();
+  nopk_barrier();
 
   // layer 2
   {
@@ -523,17 +450,17 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[e] = dq_relu(acc[ni][e] + dq_f32(bias2[ni][e]));
+        v[e] = nopk_relu(acc[ni][e] + nopk_f32(bias2[ni][e]));
       }
-      const dq_u32x2 r = dq_round4(v);
-      *reinterpret_cast<dq_u32x2*>(&z2[c][row][o]) = r;
+      const nopk_u32x2 r = nopk_round4(v);
+      *reinterpret_cast<nopk_u32x2*>(&z2[c][row][o]) = r;
       if (z2s && row0 + row < G) {
-        *reinterpret_cast<dq_u32x2*>(
+        *reinterpret_cast<nopk_u32x2*>(
             z2s + ((long long)c * G + row0 + row) * DQ_H + o) = r;
       }
     }
   }
-  dq_barrier();
+  nopk_barrier();
 
   // layer 3: D[a][row]
   f32x4 y = {0.f, 0.f, 0.f, 0.f};
@@ -544,9 +471,9 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
           &z2[c][lane & 15][kc * 32 + (lane >> 4) * 8]);
       y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f3[kc], bf, y, 0, 0, 0);
     }
-    if (c && lane < 16) ym[lane] = y[0] + dq_f32(bias3[0]);
+    if (c && lane < 16) ym[lane] = y[0] + nopk_f32(bias3[0]);
   }
-  dq_barrier();
+  nopk_barrier();
   if (l3 && !c) {
     const int row = lane & 15;
     if (row0 + row < N) {
@@ -556,7 +483,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
         const int a = wq * 16 + (lane >> 4) * 4 + e;
         if (a < A) {
           q[(long long)(row0 + row) * A + a] =
-              dq_round1((y[e] + dq_f32(bias3[e])) - m);
+              nopk_round1((y[e] + nopk_f32(bias3[e])) - m);
         }
       }
     }
@@ -567,7 +494,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_fwd(
 
 // grid ceil(G / 16). dq [>= G][A] dense, z1s / z2s [2][G][256], w2t
 // [2][256][256], w3t [256][32], w3m [256] -> dz1, dz2 [2][G][256], d3m [G]
-DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
+NOPK_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
     const bf16raw* __restrict__ dq, const bf16raw* __restrict__ z1s,
     const bf16raw* __restrict__ z2s, const bf16raw* __restrict__ w2t,
     const bf16raw* __restrict__ w3t, const bf16raw* __restrict__ w3m,
@@ -584,7 +511,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
   const int out0 = (wave & 3) * 64;
   const int row0 = blockIdx.x * DRLA_DQ_BM;
   const int row = lane & 15;  // the row of this lane's accumulators
-  const long long grow = (long long)c * G + dq_min(row0 + row, G - 1);
+  const long long grow = (long long)c * G + nopk_min(row0 + row, G - 1);
 
   // weights and both masks, requested before anything is used
   DqW256 f2;
@@ -605,11 +532,11 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
   {
     const int r = tid >> 5, a = tid & 31;
     const bool in = a < A && row0 + r < G;
-    const bf16raw v = dq[(long long)dq_min(row0 + r, G - 1) * A +
-                         dq_min(a, A - 1)];
+    const bf16raw v = dq[(long long)nopk_min(row0 + r, G - 1) * A +
+                         nopk_min(a, A - 1)];
     d3[r][a] = in ? v : (bf16raw)0;
   }
-  dq_barrier();
+  nopk_barrier();
   // d3m = -sum_a dQ, f32 in index order, rounded to bf16
   if (tid < DRLA_DQ_BM) {
     float s = 0.f;
@@ -617,13 +544,13 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
     for (int j = 0; j < DRLA_DQ_MAX_A / 8; ++j) {
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(&d3[tid][8 * j]);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) s += dq_f32((bf16raw)v[e]);
+      for (int e = 0; e < 8; ++e) s += nopk_f32((bf16raw)v[e]);
     }
-    const bf16raw m = dq_round1(-s);
-    d3mf[tid] = dq_f32(m);
+    const bf16raw m = nopk_round1(-s);
+    d3mf[tid] = nopk_f32(m);
     if (row0 + tid < G) d3m[row0 + tid] = m;
   }
-  dq_barrier();
+  nopk_barrier();
 
   // dz2 = (d3 . W3) masked by z2 > 0
   {
@@ -642,7 +569,7 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[ni][e] = m * dq_f32(w3r[ni][e]);
+        for (int e = 0; e < 4; ++e) acc[ni][e] = m * nopk_f32(w3r[ni][e]);
       }
     }
 #pragma unroll
@@ -651,16 +578,16 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[e] = dq_pos(mask2[ni][e]) ? acc[ni][e] : 0.f;
+        v[e] = nopk_pos(mask2[ni][e]) ? acc[ni][e] : 0.f;
       }
-      const dq_u32x2 r = dq_round4(v);
-      *reinterpret_cast<dq_u32x2*>(&dzl[c][row][o]) = r;
+      const nopk_u32x2 r = nopk_round4(v);
+      *reinterpret_cast<nopk_u32x2*>(&dzl[c][row][o]) = r;
       if (row0 + row < G) {
-        *reinterpret_cast<dq_u32x2*>(dz2 + grow * DQ_H + o) = r;
+        *reinterpret_cast<nopk_u32x2*>(dz2 + grow * DQ_H + o) = r;
       }
     }
   }
-  dq_barrier();
+  nopk_barrier();
 
   // dz1 = (dz2 . W2) masked by z1 > 0
   {
@@ -673,9 +600,9 @@ DQ_PRE(DRLA_DQ_TAIL_BLOCK) __global__ void drla_dq_tail_bwd(
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          v[e] = dq_pos(mask1[ni][e]) ? acc[ni][e] : 0.f;
+          v[e] = nopk_pos(mask1[ni][e]) ? acc[ni][e] : 0.f;
         }
-        *reinterpret_cast<dq_u32x2*>(dz1 + grow * DQ_H + o) = dq_round4(v);
+        *reinterpret_cast<nopk_u32x2*>(dz1 + grow * DQ_H + o) = nopk_round4(v);
       }
     }
   }
@@ -685,7 +612,7 @@ namespace {
 
 // sum over g < G of d[g][dcol] * x[g][col] (d == null: of x[g][col]): f32 in
 // row order, eight rows' loads in flight at a time
-DQ_INL float dq_col_sum(const bf16raw* __restrict__ x, int ldx, int col,
+NOPK_INL float dq_col_sum(const bf16raw* __restrict__ x, int ldx, int col,
                         const bf16raw* __restrict__ d, int ldd, int dcol,
                         int G) {
   float s = 0.f;
@@ -693,9 +620,9 @@ DQ_INL float dq_col_sum(const bf16raw* __restrict__ x, int ldx, int col,
     float xv[8], dv[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int g = dq_min(g0 + j, G - 1);
-      xv[j] = dq_f32(x[(long long)g * ldx + col]);
-      dv[j] = d ? dq_f32(d[(long long)g * ldd + dcol]) : 1.f;
+      const int g = nopk_min(g0 + j, G - 1);
+      xv[j] = nopk_f32(x[(long long)g * ldx + col]);
+      dv[j] = d ? nopk_f32(d[(long long)g * ldd + dcol]) : 1.f;
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) s += g0 + j < G ? dv[j] * xv[j] : 0.f;
@@ -712,13 +639,13 @@ DQ_INL float dq_col_sum(const bf16raw* __restrict__ x, int ldx, int col,
 //   + [0, A + 1)    dW3v row a = sum_g dQ[g][a] z2v[g], then dW3m from d3m
 //   + [0, 5)        db1v, db1m, db2v, db2m column sums; db3v and db3m
 // The tiled jobs reduce over the G live rows only: both operands are k-rows.
-DQ_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_wgrad(
+NOPK_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_wgrad(
     const bf16raw* __restrict__ feat, long long ldf,
     const bf16raw* __restrict__ dz1, const bf16raw* __restrict__ dz2,
     const bf16raw* __restrict__ z1s, const bf16raw* __restrict__ z2s,
     const bf16raw* __restrict__ dq, const bf16raw* __restrict__ d3m,
     DrlaDqGrads out, int K, int A, int G) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * DQ_SUB];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * NOPK_SUB];
   const int tid = threadIdx.x;
   const int nk = (K + 63) / 64;
   const long long br = (long long)G * DQ_H;  // one branch of a [2][G][256]
@@ -745,29 +672,29 @@ DQ_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_wgrad(
     const bool m = job == A;
     const float s = m ? dq_col_sum(z2s + br, DQ_H, tid, d3m, 1, 0, G)
                       : dq_col_sum(z2s, DQ_H, tid, dq, A, job, G);
-    (m ? out.dw3[1] : out.dw3[0] + job * DQ_H)[tid] = dq_round1(s);
+    (m ? out.dw3[1] : out.dw3[0] + job * DQ_H)[tid] = nopk_round1(s);
     return;
   }
   job -= A + 1;
   if (job < 4) {
     const bf16raw* x = (job < 2 ? dz1 : dz2) + (job & 1) * br;
     (job < 2 ? out.db1 : out.db2)[job & 1][tid] =
-        dq_round1(dq_col_sum(x, DQ_H, tid, nullptr, 0, 0, G));
+        nopk_round1(dq_col_sum(x, DQ_H, tid, nullptr, 0, 0, G));
   } else if (tid < A) {
-    out.db3[0][tid] = dq_round1(dq_col_sum(dq, A, tid, nullptr, 0, 0, G));
+    out.db3[0][tid] = nopk_round1(dq_col_sum(dq, A, tid, nullptr, 0, 0, G));
   } else if (tid == DRLA_DQ_BLOCK - 1) {
-    out.db3[1][0] = dq_round1(dq_col_sum(d3m, 1, 0, nullptr, 0, 0, G));
+    out.db3[1][0] = nopk_round1(dq_col_sum(d3m, 1, 0, nullptr, 0, 0, G));
   }
 }
 
 // grid (ceil(K / 64), ceil(N / 64)). dz1 [2][G][256], w1v / w1m [256][K] ->
 // dfeat [N][K] dense: rows < G = dz1v . W1v + dz1m . W1m in one accumulator,
 // the rest zeros; a row tile wholly past G computes nothing.
-DQ_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_l1_dgrad(
+NOPK_PRE(DRLA_DQ_BLOCK) __global__ void drla_dq_l1_dgrad(
     const bf16raw* __restrict__ dz1, const bf16raw* __restrict__ w1v,
     const bf16raw* __restrict__ w1m, bf16raw* __restrict__ dfeat, int N,
     int K, int G) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * DQ_SUB];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * NOPK_SUB];
   const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
   f32x4 acc[4];
   dq_product<false, true>(

@@ -42,73 +42,17 @@
 // dgrad: columns at or past n_live (grad_cols) are stored as zeros; a column
 // tile wholly past it computes nothing.
 //
-// Packed-f32 VALU ops stay out of this file as in maxpool.hip: every function
-// carries GG_FN, helpers are this file's own or always-inline builtins.
+// Packed-f32 VALU ops stay out of this file: every function carries NOPK_FN,
+// helpers are drla_nopk.h's (which says why), this file's own or builtins.
 
 #include "drla_kernels.h"
-#include "conv_wgrad_lds.h"
-
-#define GG_FN __attribute__((target("no-packed-fp32-ops")))
-#define GG_INL GG_FN __device__ __forceinline__
-#define GG_PRE extern "C" GG_FN __launch_bounds__(DRLA_GG_BLOCK)
+#include "drla_nopk.h"
 
 namespace {
 
-constexpr int GG_BK = DRLA_GG_BK;
-constexpr int GG_PITCH = (GG_BK + 8) * 2;   // bytes per k-contiguous LDS row
-constexpr int GG_KC_SUB = 64 * GG_PITCH;    // one k-contiguous 64-row sub-tile
-constexpr int GG_KR_ROWB = 128;             // k-rows image: 64 columns
-constexpr int GG_KR_SUB = DRLA_WG_ROWS * GG_KR_ROWB;
-static_assert(GG_BK == DRLA_WG_ROWS && DRLA_GG_BN == 64 &&
-                  DRLA_GG_BLOCK == 256,
-              "the k-rows image of conv_wgrad_lds.h is 64 k x 64 columns, "
-              "staged by 256 threads in two passes");
-static_assert((GG_PITCH / 16) % 2 == 1,
-              "odd pitch in 16-byte units: fragment reads spread over banks");
-
-typedef __attribute__((ext_vector_type(2))) float gg_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 gg_bf16x2;
-typedef __attribute__((ext_vector_type(4))) short gg_s16x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int gg_u32x2;
-
-GG_INL void gg_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-GG_INL int gg_min(int a, int b) { return a < b ? a : b; }
-// two f32 -> packed bf16, round to nearest even: one v_cvt_pk_bf16_f32
-GG_INL unsigned int gg_round_bf16x2(float a, float b) {
-  return __builtin_bit_cast(
-      unsigned int, __builtin_convertvector(gg_f32x2{a, b}, gg_bf16x2));
-}
-GG_INL gg_u32x2 gg_round_bf16x4(f32x4 v) {
-  return gg_u32x2{gg_round_bf16x2(v[0], v[1]), gg_round_bf16x2(v[2], v[3])};
-}
-// drla_wg_chunk_off<128> / drla_wg_tr_off<128> at run time. The header's
-// constexpr functions are not always_inline, so they are restated here under
-// GG_FN and held equal to them for every argument at compile time.
-GG_INL constexpr int gg_kr_chunk_off(int row, int ch) {
-  const int sw = (row & 1) | (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2);
-  return GG_KR_ROWB * row + 16 * (ch ^ sw);
-}
-GG_INL constexpr int gg_kr_tr_off(int lane, int tile) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  return gg_kr_chunk_off(8 * g + q, 2 * tile + (p >> 1)) + 8 * (p & 1);
-}
-constexpr bool gg_kr_maps_match_header() {
-  for (int row = 0; row < DRLA_WG_ROWS; ++row)
-    for (int ch = 0; ch < 8; ++ch)
-      if (gg_kr_chunk_off(row, ch) != drla_wg_chunk_off<GG_KR_ROWB>(row, ch))
-        return false;
-  for (int lane = 0; lane < 64; ++lane)
-    for (int tile = 0; tile < 4; ++tile)
-      if (gg_kr_tr_off(lane, tile) != drla_wg_tr_off<GG_KR_ROWB>(lane, tile))
-        return false;
-  return true;
-}
-static_assert(gg_kr_maps_match_header(),
-              "the k-rows maps are those conv_wgrad_lds.h proves");
+static_assert(DRLA_GG_BK == NOPK_BK && DRLA_GG_BN == 64 && DRLA_GG_BLOCK == 256,
+              "the tiles of drla_nopk.h: 64 k x 64 columns, staged by 256 "
+              "threads in two passes");
 
 // One operand's block tile: SUBS sub-tiles of 64 rows (k-contiguous) or 64
 // columns (k-rows) x 64 k. Thread slot: LDS row srow + 32 j (pass j = 0, 1),
@@ -128,7 +72,7 @@ struct GgTile {
 
   // tile0: first row (k-contiguous) / column (k-rows) of the block's tile;
   // nmax: how many the matrix has
-  GG_INL void init(const bf16raw* p_, long long ld_, int tile0, int nmax,
+  NOPK_INL void init(const bf16raw* p_, long long ld_, int tile0, int nmax,
                    int kmax_, int tid) {
     p = p_; ld = ld_; kmax = kmax_;
     srow = tid >> 3; sch = tid & 7;
@@ -140,18 +84,18 @@ struct GgTile {
         if constexpr (KROWS) {
           const int c = tile0 + 64 * s + 8 * sch;
           live |= (unsigned int)(c < nmax) << (2 * s + j);
-          off[s][j] = gg_min(c, nmax - 8);
+          off[s][j] = nopk_min(c, nmax - 8);
         } else {
           const int row = tile0 + 64 * s + srow + 32 * j;
           live |= (unsigned int)(row < nmax) << (2 * s + j);
-          off[s][j] = (long long)gg_min(row, nmax - 1) * ld;
+          off[s][j] = (long long)nopk_min(row, nmax - 1) * ld;
         }
       }
     }
   }
 
   // global -> registers for chunk k0 of a split that ends at k_end
-  GG_INL void load(int k0, int k_end) {
+  NOPK_INL void load(int k0, int k_end) {
     klive = 0;
     long long koff[2];
 #pragma unroll
@@ -159,11 +103,11 @@ struct GgTile {
       if constexpr (KROWS) {
         const int k = k0 + srow + 32 * j;
         klive |= (unsigned int)(k < k_end) << j;
-        koff[j] = (long long)gg_min(k, kmax - 1) * ld;
+        koff[j] = (long long)nopk_min(k, kmax - 1) * ld;
       } else {
         const int k = k0 + 8 * sch;
         klive |= (unsigned int)(k < k_end) << j;
-        koff[j] = gg_min(k, kmax - 8);
+        koff[j] = nopk_min(k, kmax - 8);
       }
     }
 #pragma unroll
@@ -176,38 +120,28 @@ struct GgTile {
   }
 
   // registers -> LDS image; pieces outside the matrix or the split are zeros
-  GG_INL void store(unsigned char* lds) const {
-    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  NOPK_INL void store(unsigned char* lds) const {
 #pragma unroll
     for (int s = 0; s < SUBS; ++s) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const bool in = ((live >> (2 * s + j)) & (klive >> j) & 1u) != 0;
-        const int o = KROWS ? s * GG_KR_SUB + gg_kr_chunk_off(srow + 32 * j, sch)
-                            : s * GG_KC_SUB + (srow + 32 * j) * GG_PITCH +
+        const int o = KROWS ? s * NOPK_KR_SUB + nopk_chunk_off(srow + 32 * j, sch)
+                            : s * NOPK_KC_SUB + (srow + 32 * j) * NOPK_PITCH +
                                   16 * sch;
-        *reinterpret_cast<bf16x8*>(lds + o) = in ? r[s][j] : z;
+        *reinterpret_cast<bf16x8*>(lds + o) = in ? r[s][j] : nopk_zero8();
       }
     }
   }
 
   // 16x16x32 operand of 16-wide tile t16, k-step ks: lane l gets element
   // (t16 * 16 + l % 16, 32 ks + 8 (l / 16) + e) in e = 0..7. EXEC is full.
-  static GG_INL bf16x8 frag(const unsigned char* lds, int t16, int ks,
+  static NOPK_INL bf16x8 frag(const unsigned char* lds, int t16, int ks,
                             int lane) {
     if constexpr (KROWS) {
-      typedef __attribute__((address_space(3))) gg_s16x4* lds_ptr;
-      const unsigned char* q = lds + (t16 >> 2) * GG_KR_SUB +
-                               gg_kr_tr_off(lane, t16 & 3) +
-                               32 * ks * GG_KR_ROWB;
-      const gg_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)q);
-      const gg_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (lds_ptr)(q + 4 * GG_KR_ROWB));
-      return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      return nopk_frag_kr(lds + (t16 >> 2) * NOPK_KR_SUB, t16 & 3, ks, lane);
     } else {
-      return *reinterpret_cast<const bf16x8*>(
-          lds + (t16 * 16 + (lane & 15)) * GG_PITCH + 64 * ks +
-          16 * (lane >> 4));
+      return nopk_frag_kc(lds, NOPK_PITCH, t16, ks, lane);
     }
   }
 };
@@ -216,13 +150,13 @@ struct GgTile {
 // ldc), columns >= n_live as zeros. ws != null: this block's split of k as
 // f32 to ws[blockIdx.z][Mo][No].
 template <bool A_KROWS, bool B_KROWS, int MT>
-GG_INL void gate_gemm_impl(const bf16raw* __restrict__ a, long long lda,
+NOPK_INL void gate_gemm_impl(const bf16raw* __restrict__ a, long long lda,
                            const bf16raw* __restrict__ b, long long ldb,
                            bf16raw* __restrict__ c, long long ldc,
                            float* __restrict__ ws, int Mo, int No, int Kc,
                            int n_live) {
-  constexpr int A_SUB = A_KROWS ? GG_KR_SUB : GG_KC_SUB;
-  constexpr int B_SUB = B_KROWS ? GG_KR_SUB : GG_KC_SUB;
+  constexpr int A_SUB = A_KROWS ? NOPK_KR_SUB : NOPK_KC_SUB;
+  constexpr int B_SUB = B_KROWS ? NOPK_KR_SUB : NOPK_KC_SUB;
   constexpr int NFRAG = DRLA_GG_BN / 16;
   __shared__ __attribute__((aligned(16))) unsigned char As[2][MT * A_SUB];
   __shared__ __attribute__((aligned(16))) unsigned char Bs[2][B_SUB];
@@ -240,13 +174,13 @@ GG_INL void gate_gemm_impl(const bf16raw* __restrict__ a, long long lda,
   }
 
   // the split's k range, in whole chunks; an empty one stores zeros
-  const int chunks = (Kc + GG_BK - 1) / GG_BK;
+  const int chunks = (Kc + NOPK_BK - 1) / NOPK_BK;
   const int per = (chunks + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int k_begin = gg_min((int)blockIdx.z * per, chunks) * GG_BK;
-  const int k_end = gg_min(k_begin + per * GG_BK, Kc);
+  const int k_begin = nopk_min((int)blockIdx.z * per, chunks) * NOPK_BK;
+  const int k_end = nopk_min(k_begin + per * NOPK_BK, Kc);
   // block-uniform: a dead column tile computes nothing
   const int nchunks =
-      n0 >= n_live ? 0 : (k_end - k_begin + GG_BK - 1) / GG_BK;
+      n0 >= n_live ? 0 : (k_end - k_begin + NOPK_BK - 1) / NOPK_BK;
 
   if (nchunks > 0) {
     GgTile<A_KROWS, MT> ta;
@@ -257,20 +191,20 @@ GG_INL void gate_gemm_impl(const bf16raw* __restrict__ a, long long lda,
     tb.load(k_begin, k_end);
     ta.store(As[0]);
     tb.store(Bs[0]);
-    ta.load(k_begin + GG_BK, k_end);
-    tb.load(k_begin + GG_BK, k_end);
-    gg_barrier();
+    ta.load(k_begin + NOPK_BK, k_end);
+    tb.load(k_begin + NOPK_BK, k_end);
+    nopk_barrier();
 #pragma unroll 1
     for (int t = 0; t < nchunks; ++t) {
       const int cur = t & 1;
       if (t + 1 < nchunks) {
         ta.store(As[1 - cur]);
         tb.store(Bs[1 - cur]);
-        ta.load(k_begin + (t + 2) * GG_BK, k_end);
-        tb.load(k_begin + (t + 2) * GG_BK, k_end);
+        ta.load(k_begin + (t + 2) * NOPK_BK, k_end);
+        tb.load(k_begin + (t + 2) * NOPK_BK, k_end);
       }
 #pragma unroll
-      for (int ks = 0; ks < GG_BK / 32; ++ks) {
+      for (int ks = 0; ks < NOPK_BK / 32; ++ks) {
         bf16x8 bf[NFRAG];
 #pragma unroll
         for (int ni = 0; ni < NFRAG; ++ni) {
@@ -288,7 +222,7 @@ GG_INL void gate_gemm_impl(const bf16raw* __restrict__ a, long long lda,
           }
         }
       }
-      gg_barrier();
+      nopk_barrier();
     }
   }
 
@@ -306,8 +240,8 @@ GG_INL void gate_gemm_impl(const bf16raw* __restrict__ a, long long lda,
           f32x4 v = acc[mi][ni];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = (n + e < n_live) ? v[e] : 0.f;
-          *reinterpret_cast<gg_u32x2*>(c + (long long)m * ldc + n) =
-              gg_round_bf16x4(v);
+          *reinterpret_cast<nopk_u32x2*>(c + (long long)m * ldc + n) =
+              nopk_round4(v);
         }
       }
     }
@@ -317,7 +251,7 @@ GG_INL void gate_gemm_impl(const bf16raw* __restrict__ a, long long lda,
 }  // namespace
 
 // xh [M][K] (row stride ldx), w [K][N] (ldw) -> g [M][N] dense, or ws
-GG_PRE __global__ void drla_gate_gemm_fwd(const bf16raw* xh, long long ldx,
+NOPK_PRE(DRLA_GG_BLOCK) __global__ void drla_gate_gemm_fwd(const bf16raw* xh, long long ldx,
                              const bf16raw* w, long long ldw, bf16raw* g,
                              float* ws, int M, int K, int N) {
   gate_gemm_impl<false, true, DRLA_GG_FWD_MT>(xh, ldx, w, ldw, g, N, ws, M, N,
@@ -326,7 +260,7 @@ GG_PRE __global__ void drla_gate_gemm_fwd(const bf16raw* xh, long long ldx,
 
 // dg [M][N] (lddg), w [K][N] (ldw) -> dxh [M][K] dense; columns >= grad_cols
 // are zeros
-GG_PRE __global__ void drla_gate_gemm_dgrad(const bf16raw* dg, long long lddg,
+NOPK_PRE(DRLA_GG_BLOCK) __global__ void drla_gate_gemm_dgrad(const bf16raw* dg, long long lddg,
                                const bf16raw* w, long long ldw, bf16raw* dxh,
                                int M, int K, int N, int grad_cols) {
   gate_gemm_impl<false, false, DRLA_GG_DGRAD_MT>(dg, lddg, w, ldw, dxh, K,
@@ -334,28 +268,16 @@ GG_PRE __global__ void drla_gate_gemm_dgrad(const bf16raw* dg, long long lddg,
 }
 
 // xh [M][K] (ldx), dg [M][N] (lddg) -> dw [K][N] dense
-GG_PRE __global__ void drla_gate_gemm_wgrad(const bf16raw* xh, long long ldx,
+NOPK_PRE(DRLA_GG_BLOCK) __global__ void drla_gate_gemm_wgrad(const bf16raw* xh, long long ldx,
                                const bf16raw* dg, long long lddg, bf16raw* dw,
                                int M, int K, int N) {
   gate_gemm_impl<true, true, DRLA_GG_WGRAD_MT>(xh, ldx, dg, lddg, dw, N,
                                                nullptr, K, N, M, N);
 }
 
-// g[i] = bf16(ws[0][i] + ws[1][i] + ... + ws[S-1][i]), four outputs per
-// thread and step; n4 = M * N / 4
-GG_PRE __global__ void drla_gate_gemm_reduce(const float* __restrict__ ws,
-                                bf16raw* __restrict__ g, long long n4,
-                                int S) {
-  const long long stride = (long long)gridDim.x * DRLA_GG_BLOCK;
-  for (long long i = (long long)blockIdx.x * DRLA_GG_BLOCK + threadIdx.x;
-       i < n4; i += stride) {
-    f32x4 sum = *reinterpret_cast<const f32x4*>(ws + 4 * i);
-    for (int s = 1; s < S; ++s) {
-      const f32x4 v =
-          *reinterpret_cast<const f32x4*>(ws + 4 * ((long long)s * n4 + i));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sum[e] += v[e];
-    }
-    *reinterpret_cast<gg_u32x2*>(g + 4 * i) = gg_round_bf16x4(sum);
-  }
+// g[i] = bf16(ws[0][i] + ws[1][i] + ... + ws[S-1][i]); n4 = M * N / 4
+NOPK_PRE(DRLA_GG_BLOCK) __global__ void drla_gate_gemm_reduce(
+    const float* __restrict__ ws, bf16raw* __restrict__ g, long long n4,
+    int S) {
+  nopk_split_reduce<DRLA_GG_BLOCK, false>(ws, nullptr, g, n4, 0, S);
 }

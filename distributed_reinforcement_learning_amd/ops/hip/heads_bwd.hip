@@ -36,15 +36,11 @@
 // 16-byte loads per thread, or one f32) and pick their fragments out of it
 // with 2-byte LDS reads.
 //
-// Packed-f32 VALU ops stay out of this file as in maxpool.hip: every function
-// carries HB_FN, helpers are this file's own or always-inline builtins.
+// Packed-f32 VALU ops stay out of this file: every function carries NOPK_FN,
+// helpers are drla_nopk.h's (which says why), this file's own or builtins.
 
 #include "drla_kernels.h"
-#include "conv_wgrad_lds.h"
-
-#define HB_FN __attribute__((target("no-packed-fp32-ops")))
-#define HB_INL HB_FN __device__ __forceinline__
-#define HB_PRE(threads) extern "C" HB_FN __launch_bounds__(threads)
+#include "drla_nopk.h"
 
 namespace {
 
@@ -54,8 +50,6 @@ constexpr int HB_DH_LD = HB_H + 4;    // f32 dh tile rows, elements
 constexpr int HB_D3_LD = MH_MAX_A + 8;
 constexpr int HB_BLOCK = 512;         // drla_mlp_heads_bwd
 constexpr int HB_WG_BLOCK = 256;      // drla_heads_wgrad
-constexpr int HB_ROWB = 128;          // k-rows image: 64 columns of bf16
-constexpr int HB_SUB = DRLA_WG_ROWS * HB_ROWB;
 static_assert(HB_H == 4 * 64 && MH_BM == 16 && MH_MAX_A == 32,
               "two chains x four waves x 64 output columns, 16-row blocks, "
               "layer 3 one 32-deep k-step");
@@ -64,45 +58,19 @@ static_assert((HB_ACT_LD * 2 / 16) % 2 == 1,
 // the narrow jobs' flat chunk: 64 rows of at most 32 elements plus up to 7
 // elements of misalignment, in whole 16-byte vectors
 constexpr int HB_FLAT_VECS = DRLA_WG_ROWS * MH_MAX_A / 8 + 1;
-static_assert(HB_FLAT_VECS * 16 <= HB_SUB && HB_FLAT_VECS <= HB_WG_BLOCK + 1,
+static_assert(HB_FLAT_VECS * 16 <= NOPK_KR_SUB && HB_FLAT_VECS <= HB_WG_BLOCK + 1,
               "the flat chunk fits the dz image it replaces; a thread loads "
               "vector tid, thread 0 also vector 256");
 
-typedef __attribute__((ext_vector_type(2))) float hb_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 hb_bf16x2;
-typedef __attribute__((ext_vector_type(4))) short hb_s16x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int hb_u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int hb_u32x4;
-
-HB_INL void hb_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-HB_INL int hb_min(int a, int b) { return a < b ? a : b; }
-HB_INL long long hb_minll(long long a, long long b) { return a < b ? a : b; }
-HB_INL float hb_f32(bf16raw u) {
-  return __builtin_bit_cast(float, (unsigned int)u << 16);
-}
-// two f32 -> packed bf16, round to nearest even: one v_cvt_pk_bf16_f32
-HB_INL unsigned int hb_round2(float a, float b) {
-  return __builtin_bit_cast(
-      unsigned int, __builtin_convertvector(hb_f32x2{a, b}, hb_bf16x2));
-}
-HB_INL hb_u32x2 hb_round4(f32x4 v) {
-  return hb_u32x2{hb_round2(v[0], v[1]), hb_round2(v[2], v[3])};
-}
-HB_INL bf16raw hb_round1(float a) {
-  return (bf16raw)(hb_round2(a, a) & 0xffffu);
-}
-HB_INL void hb_atomic_add(float* p, float v) {
+NOPK_INL long long hb_minll(long long a, long long b) { return a < b ? a : b; }
+NOPK_INL void hb_atomic_add(float* p, float v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // v summed over the 16 lanes of a DPP row (the lanes that share lane / 16);
 // every lane of the row gets the sum. quad_perm [1,0,3,2], [2,3,0,1],
 // row_half_mirror, row_mirror.
-HB_INL float hb_row_sum(float v) {
+NOPK_INL float hb_row_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
            0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
@@ -114,41 +82,6 @@ HB_INL float hb_row_sum(float v) {
   return v;
 }
 
-// drla_wg_chunk_off<128> / drla_wg_tr_off<128> at run time, restated under
-// HB_FN (the header's functions are not always_inline) and held equal to
-// them for every argument at compile time, with the store slot map
-HB_INL constexpr int hb_kr_chunk_off(int row, int ch) {
-  const int sw = (row & 1) | (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2);
-  return HB_ROWB * row + 16 * (ch ^ sw);
-}
-HB_INL constexpr int hb_kr_tr_off(int lane, int tile) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  return hb_kr_chunk_off(8 * g + q, 2 * tile + (p >> 1)) + 8 * (p & 1);
-}
-// thread tid stores row tid / 8 + 32 j, chunk tid % 8 in pass j
-HB_INL constexpr int hb_slot_row(int tid, int j) { return (tid >> 3) + 32 * j; }
-HB_INL constexpr int hb_slot_ch(int tid) { return tid & 7; }
-constexpr bool hb_kr_maps_match_header() {
-  for (int row = 0; row < DRLA_WG_ROWS; ++row)
-    for (int ch = 0; ch < 8; ++ch)
-      if (hb_kr_chunk_off(row, ch) != drla_wg_chunk_off<HB_ROWB>(row, ch))
-        return false;
-  for (int lane = 0; lane < 64; ++lane)
-    for (int tile = 0; tile < 4; ++tile)
-      if (hb_kr_tr_off(lane, tile) != drla_wg_tr_off<HB_ROWB>(lane, tile))
-        return false;
-  for (int tid = 0; tid < HB_WG_BLOCK; ++tid)
-    for (int j = 0; j < 2; ++j) {
-      const DrlaWgSlot s = drla_wg_b_slot<64>(tid, j);
-      if (s.row != hb_slot_row(tid, j) || s.ch != hb_slot_ch(tid))
-        return false;
-    }
-  return true;
-}
-static_assert(hb_kr_maps_match_header(),
-              "the k-rows maps and the store slots are those conv_wgrad_lds.h "
-              "proves (drla_wg_b_slot<64>, two passes of 256 threads)");
-
 // ---- drla_mlp_heads_bwd: per-wave pieces ----------------------------------
 
 // half of a wave's slice of a [256][256] first operand: rows out0 + 16 ni +
@@ -156,7 +89,7 @@ static_assert(hb_kr_maps_match_header(),
 struct HbW128 {
   bf16x8 a[4][4];
 };
-HB_INL void hb_load_w128(HbW128& f, const bf16raw* __restrict__ w, int out0,
+NOPK_INL void hb_load_w128(HbW128& f, const bf16raw* __restrict__ w, int out0,
                          int k0, int lane) {
 #pragma unroll
   for (int kc = 0; kc < 4; ++kc) {
@@ -170,7 +103,7 @@ HB_INL void hb_load_w128(HbW128& f, const bf16raw* __restrict__ w, int out0,
 }
 // acc[ni] += D[out0 + 16 ni + 4 (l / 16) + e][row l % 16] over the 128 k
 // from k0 of act [16][HB_ACT_LD], k ascending
-HB_INL void hb_mma128(f32x4 (&acc)[4], const HbW128& f,
+NOPK_INL void hb_mma128(f32x4 (&acc)[4], const HbW128& f,
                       const bf16raw (*act)[HB_ACT_LD], int k0, int lane) {
 #pragma unroll
   for (int kc = 0; kc < 4; ++kc) {
@@ -185,7 +118,7 @@ HB_INL void hb_mma128(f32x4 (&acc)[4], const HbW128& f,
 }
 // the four values a lane's acc[ni] goes with, of a [rows][256] bf16 matrix
 // row: one 8-byte load per ni
-HB_INL void hb_load_side(ushort4v (&s)[4], const bf16raw* __restrict__ row,
+NOPK_INL void hb_load_side(ushort4v (&s)[4], const bf16raw* __restrict__ row,
                          int out0, int lane) {
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
@@ -198,7 +131,7 @@ HB_INL void hb_load_side(ushort4v (&s)[4], const bf16raw* __restrict__ row,
 // column sums of the unrounded v go to bias[256] with one atomic per column
 // (lane 16 g + j owns column out0 + 16 (j / 4) + 4 g + j % 4); v rounded to
 // bf16 goes to the LDS image img [16][HB_ACT_LD].
-HB_INL void hb_masked_out(const f32x4 (&acc)[4], const ushort4v (&mask)[4],
+NOPK_INL void hb_masked_out(const f32x4 (&acc)[4], const ushort4v (&mask)[4],
                           bool live, bf16raw (*img)[HB_ACT_LD],
                           float* __restrict__ bias, int out0, int lane) {
   const int row = lane & 15, g = lane >> 4;
@@ -208,19 +141,19 @@ HB_INL void hb_masked_out(const f32x4 (&acc)[4], const ushort4v (&mask)[4],
     f32x4 v;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      v[e] = (live && hb_f32(mask[ni][e]) > 0.f) ? acc[ni][e] : 0.f;
+      v[e] = (live && nopk_f32(mask[ni][e]) > 0.f) ? acc[ni][e] : 0.f;
       const float s = hb_row_sum(v[e]);
       mine = (row == ni * 4 + e) ? s : mine;
     }
-    *reinterpret_cast<hb_u32x2*>(&img[row][out0 + ni * 16 + g * 4]) =
-        hb_round4(v);
+    *reinterpret_cast<nopk_u32x2*>(&img[row][out0 + ni * 16 + g * 4]) =
+        nopk_round4(v);
   }
   hb_atomic_add(bias + out0 + 16 * (row >> 2) + 4 * g + (row & 3), mine);
 }
 
 // the block's two [16][256] bf16 images (policy, value) -> global rows, two
 // 16-byte stores per thread; rows < N only
-HB_INL void hb_store_images(const bf16raw (*imgp)[HB_ACT_LD],
+NOPK_INL void hb_store_images(const bf16raw (*imgp)[HB_ACT_LD],
                             const bf16raw (*imgv)[HB_ACT_LD],
                             bf16raw* __restrict__ outp,
                             bf16raw* __restrict__ outv, int row0, int N,
@@ -232,8 +165,8 @@ HB_INL void hb_store_images(const bf16raw (*imgp)[HB_ACT_LD],
     bf16raw* d = out + (long long)(row0 + r) * HB_H;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      *reinterpret_cast<hb_u32x4*>(d + 8 * (ch + 16 * j)) =
-          *reinterpret_cast<const hb_u32x4*>(&img[r][8 * (ch + 16 * j)]);
+      *reinterpret_cast<nopk_u32x4*>(d + 8 * (ch + 16 * j)) =
+          *reinterpret_cast<const nopk_u32x4*>(&img[r][8 * (ch + 16 * j)]);
     }
   }
 }
@@ -244,7 +177,7 @@ HB_INL void hb_store_images(const bf16raw (*imgp)[HB_ACT_LD],
 // pad(W3p^T), wT2p / wT1p / wT2v / wT1v [256][256] = W^T, W3v [1][256] as it
 // is (the value out layer's backward is an outer product). dh is written,
 // every element once; the six bias sums are added to and must come in zero.
-HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
+NOPK_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
     const bf16raw* __restrict__ dlogits,   // [N,A]
     const float* __restrict__ dvalue,      // [N]
     const bf16raw* __restrict__ stash,     // [N,5*256]
@@ -273,7 +206,7 @@ HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
   const int row0 = blockIdx.x * MH_BM;
   const int row = lane & 15;  // the row of this lane's accumulators
   const bool live = row0 + row < N;
-  const long long grow = hb_min(row0 + row, N - 1);
+  const long long grow = nopk_min(row0 + row, N - 1);
   const long long soff = (long long)N * HB_H;
   const bf16raw* a1 = stash + (c ? 2 * soff : 0);
   const bf16raw* a2 = a1 + soff;
@@ -302,26 +235,26 @@ HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
   {
     const int r = tid >> 5, a = tid & 31;
     const bool in = a < A && row0 + r < N;
-    const bf16raw v = dlogits[(long long)hb_min(row0 + r, N - 1) * A +
-                              hb_min(a, A - 1)];
+    const bf16raw v = dlogits[(long long)nopk_min(row0 + r, N - 1) * A +
+                              nopk_min(a, A - 1)];
     d3[r][a] = in ? v : (bf16raw)0;
   }
   // db3v: the block's dvalue rows, summed in row order by one thread
   if (tid == HB_BLOCK - 1) {
     float x[MH_BM];
 #pragma unroll
-    for (int r = 0; r < MH_BM; ++r) x[r] = dvalue[hb_min(row0 + r, N - 1)];
+    for (int r = 0; r < MH_BM; ++r) x[r] = dvalue[nopk_min(row0 + r, N - 1)];
     float s = 0.f;
 #pragma unroll
     for (int r = 0; r < MH_BM; ++r) s += row0 + r < N ? x[r] : 0.f;
     hb_atomic_add(db3v, s);
   }
-  hb_barrier();
+  nopk_barrier();
   // db3p: dlogits column sums in row order (dead rows are zeros)
   if (tid < A) {
     float s = 0.f;
 #pragma unroll
-    for (int r = 0; r < MH_BM; ++r) s += hb_f32(d3[r][tid]);
+    for (int r = 0; r < MH_BM; ++r) s += nopk_f32(d3[r][tid]);
     hb_atomic_add(db3p + tid, s);
   }
 
@@ -341,7 +274,7 @@ HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[ni][e] = dv * hb_f32(w3r[ni][e]);
+        for (int e = 0; e < 4; ++e) acc[ni][e] = dv * nopk_f32(w3r[ni][e]);
       }
     }
     hb_masked_out(acc, mask2, live, dzl[c][0], c ? db2v : db2p, out0, lane);
@@ -349,7 +282,7 @@ HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
   // the second mask takes the registers layer 3 has left; W2^T's MFMAs run
   // in front of its first use
   hb_load_side(mask1, a1 + grow * HB_H, out0, lane);
-  hb_barrier();
+  nopk_barrier();
   hb_store_images(dzl[0][0], dzl[1][0], dz2p, dz2v, row0, N, tid);
 
   // dz1 = (dz2 . W2) masked by a1 > 0
@@ -364,7 +297,7 @@ HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
     hb_load_w128(f1hi, wT1, out0, 128, lane);
     hb_masked_out(acc, mask1, live, dzl[c][1], c ? db1v : db1p, out0, lane);
   }
-  hb_barrier();
+  nopk_barrier();
   hb_store_images(dzl[0][1], dzl[1][1], dz1p, dz1v, row0, N, tid);
 
   // dh = dz1p . W1p + dz1v . W1v: the value chain's f32 tile goes through
@@ -382,7 +315,7 @@ HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
             &dht[row][out0 + ni * 16 + (lane >> 4) * 4]) = acc[ni];
       }
     }
-    hb_barrier();
+    nopk_barrier();
     if (c == 0 && live) {
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
@@ -404,7 +337,7 @@ HB_PRE(HB_BLOCK) __global__ void drla_mlp_heads_bwd(
 //   0: dW1p = dz1p^T . hb     3: dW2v = dz2v^T . a1v
 //   1: dW2p = dz2p^T . a1p    4: dW3p = dlogits^T . a2p   M = A
 //   2: dW1v = dz1v^T . hb     5: dW3v = dvalue^T . a2v    M = 1
-HB_PRE(HB_WG_BLOCK) __global__ void drla_heads_wgrad(
+NOPK_PRE(HB_WG_BLOCK) __global__ void drla_heads_wgrad(
     const bf16raw* __restrict__ dz1p, const bf16raw* __restrict__ dz2p,
     const bf16raw* __restrict__ dz1v, const bf16raw* __restrict__ dz2v,
     const bf16raw* __restrict__ dlogits,  // [N,A]
@@ -420,13 +353,13 @@ HB_PRE(HB_WG_BLOCK) __global__ void drla_heads_wgrad(
     bf16raw* __restrict__ db2v, bf16raw* __restrict__ db3v,
     int N, int A) {
   // [dz: 2 buffers][act: 2 buffers]
-  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * HB_SUB];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * NOPK_KR_SUB];
   const int tid = threadIdx.x;
   const int bid = blockIdx.x;
   if (bid == 72) {
     const int total = 4 * 256 + A + 1;
     for (int i = tid; i < total; i += HB_WG_BLOCK) {
-      const bf16raw v = hb_round1(ws_tail[i]);
+      const bf16raw v = nopk_round1(ws_tail[i]);
       if (i < 256)            db1p[i] = v;
       else if (i < 512)       db2p[i - 256] = v;
       else if (i < 512 + A)   db3p[i - 512] = v;
@@ -462,7 +395,7 @@ HB_PRE(HB_WG_BLOCK) __global__ void drla_heads_wgrad(
   const int m0 = mt * 64;
   const int n0 = nt * 64;
   const int wave = tid >> 6, lane = tid & 63;
-  const int srow = hb_slot_row(tid, 0), sch = hb_slot_ch(tid);
+  const int srow = nopk_slot_row(tid, 0), sch = nopk_slot_ch(tid);
   const bool wide = job < 4;  // block-uniform
   const int nchunks = (N + DRLA_WG_ROWS - 1) / DRLA_WG_ROWS;
 
@@ -475,70 +408,64 @@ HB_PRE(HB_WG_BLOCK) __global__ void drla_heads_wgrad(
   // dvalue, one element per row.
   const unsigned long long dl_addr = (unsigned long long)dlogits;
   const int mis = job == 4 ? (int)((dl_addr & 15) >> 1) : 0;
-  const hb_u32x4* dl_vec =
-      reinterpret_cast<const hb_u32x4*>(dl_addr & ~15ull);
+  const nopk_u32x4* dl_vec =
+      reinterpret_cast<const nopk_u32x4*>(dl_addr & ~15ull);
   const long long vlast = (mis + (long long)N * A - 1) >> 3;
   const int An = job == 4 ? A : 1;  // row pitch of the flat chunk
 
   unsigned char* As = lds;
-  unsigned char* Bs = lds + 2 * HB_SUB;
+  unsigned char* Bs = lds + 2 * NOPK_KR_SUB;
   bf16x8 r_a[2], r_b[2];
-  hb_u32x4 r_n0, r_n1;
+  nopk_u32x4 r_n0, r_n1;
   float r_dv;
   unsigned int klive = 0;
 
-  auto load = [&](int t) HB_FN __attribute__((always_inline)) {
+  auto load = [&](int t) NOPK_LAMBDA {
     klive = 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int k = t * DRLA_WG_ROWS + srow + 32 * j;
       klive |= (unsigned int)(k < N) << j;
-      const long long koff = (long long)hb_min(k, N - 1) * HB_H + 8 * sch;
+      const long long koff = (long long)nopk_min(k, N - 1) * HB_H + 8 * sch;
       r_b[j] = *reinterpret_cast<const bf16x8*>(act + koff + n0);
       if (wide) r_a[j] = *reinterpret_cast<const bf16x8*>(dz + koff + m0);
     }
     if (job == 4) {
       const long long v0 = 8ll * A * t;
-      r_n0 = dl_vec[hb_minll(v0 + hb_min(tid, 8 * A), vlast)];
+      r_n0 = dl_vec[hb_minll(v0 + nopk_min(tid, 8 * A), vlast)];
       r_n1 = dl_vec[hb_minll(v0 + HB_WG_BLOCK, vlast)];
     } else if (job == 5) {
-      r_dv = dvalue[hb_min(t * DRLA_WG_ROWS + (tid & 63), N - 1)];
+      r_dv = dvalue[nopk_min(t * DRLA_WG_ROWS + (tid & 63), N - 1)];
     }
   };
-  auto store = [&](int buf) HB_FN __attribute__((always_inline)) {
-    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto store = [&](int buf) NOPK_LAMBDA {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const bool in = ((klive >> j) & 1u) != 0;
-      const int o = hb_kr_chunk_off(srow + 32 * j, sch);
-      *reinterpret_cast<bf16x8*>(Bs + buf * HB_SUB + o) = in ? r_b[j] : z;
+      const int o = nopk_chunk_off(srow + 32 * j, sch);
+      *reinterpret_cast<bf16x8*>(Bs + buf * NOPK_KR_SUB + o) =
+          in ? r_b[j] : nopk_zero8();
       if (wide) {
-        *reinterpret_cast<bf16x8*>(As + buf * HB_SUB + o) = in ? r_a[j] : z;
+        *reinterpret_cast<bf16x8*>(As + buf * NOPK_KR_SUB + o) =
+            in ? r_a[j] : nopk_zero8();
       }
     }
     if (job == 4) {
-      *reinterpret_cast<hb_u32x4*>(As + buf * HB_SUB + 16 * tid) = r_n0;
+      *reinterpret_cast<nopk_u32x4*>(As + buf * NOPK_KR_SUB + 16 * tid) = r_n0;
       if (tid == 0) {
-        *reinterpret_cast<hb_u32x4*>(As + buf * HB_SUB + 16 * HB_WG_BLOCK) =
+        *reinterpret_cast<nopk_u32x4*>(As + buf * NOPK_KR_SUB + 16 * HB_WG_BLOCK) =
             r_n1;
       }
     } else if (job == 5) {
       if (tid < 64) {
-        *reinterpret_cast<bf16raw*>(As + buf * HB_SUB + 2 * tid) =
-            hb_round1(r_dv);
+        *reinterpret_cast<bf16raw*>(As + buf * NOPK_KR_SUB + 2 * tid) =
+            nopk_round1(r_dv);
       }
     }
   };
-  // 16x16x32 operand of 16-wide tile t16, k-step ks, from a k-rows image:
-  // lane l gets element (k = 32 ks + 8 (l / 16) + e, column 16 t16 + l % 16)
   auto frag = [&](const unsigned char* img, int t16, int ks)
-                  HB_FN __attribute__((always_inline)) -> bf16x8 {
-    typedef __attribute__((address_space(3))) hb_s16x4* lds_ptr;
-    const unsigned char* q = img + hb_kr_tr_off(lane, t16) + 32 * ks * HB_ROWB;
-    const hb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)q);
-    const hb_s16x4 hi =
-        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(q + 4 * HB_ROWB));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                  NOPK_LAMBDA -> bf16x8 {
+    return nopk_frag_kr(img, t16, ks, lane);
   };
 
   f32x4 acc[4];
@@ -551,7 +478,7 @@ HB_PRE(HB_WG_BLOCK) __global__ void drla_heads_wgrad(
   load(0);
   store(0);
   load(1);
-  hb_barrier();
+  nopk_barrier();
 #pragma unroll 1
   for (int t = 0; t < nchunks; ++t) {
     const int cur = t & 1;
@@ -564,36 +491,36 @@ HB_PRE(HB_WG_BLOCK) __global__ void drla_heads_wgrad(
       for (int ks = 0; ks < DRLA_WG_ROWS / 32; ++ks) {
         bf16x8 af;
         if (wide) {
-          af = frag(As + cur * HB_SUB, wave, ks);
+          af = frag(As + cur * NOPK_KR_SUB, wave, ks);
         } else {
           const bf16raw* flat =
-              reinterpret_cast<const bf16raw*>(As + cur * HB_SUB);
+              reinterpret_cast<const bf16raw*>(As + cur * NOPK_KR_SUB);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const int k = 32 * ks + 8 * (lane >> 4) + e;
-            const bf16raw v = flat[mis + k * An + hb_min(mloc, M - 1)];
+            const bf16raw v = flat[mis + k * An + nopk_min(mloc, M - 1)];
             af[e] = (mloc < M && t * DRLA_WG_ROWS + k < N) ? (short)v
                                                            : (short)0;
           }
         }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
-          const bf16x8 bf = frag(Bs + cur * HB_SUB, ni, ks);
+          const bf16x8 bf = frag(Bs + cur * NOPK_KR_SUB, ni, ks);
           // B first: D[n][m], a lane holds n = 4 (l / 16) .. + 3 of m = l % 16
           acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf, af, acc[ni],
                                                             0, 0, 0);
         }
       }
     }
-    hb_barrier();
+    nopk_barrier();
   }
   const int m = m0 + mloc;
   if (m < M) {
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
       const int n = n0 + ni * 16 + (lane >> 4) * 4;
-      *reinterpret_cast<hb_u32x2*>(out + (long long)m * HB_H + n) =
-          hb_round4(acc[ni]);
+      *reinterpret_cast<nopk_u32x2*>(out + (long long)m * HB_H + n) =
+          nopk_round4(acc[ni]);
     }
   }
 }

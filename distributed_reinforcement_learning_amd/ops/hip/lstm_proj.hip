@@ -49,117 +49,18 @@
 // outside its matrix is loaded from a clamped (valid) address and staged as
 // zeros, EXEC is full around the transposed reads, stores are predicated.
 //
-// Packed-f32 VALU ops stay out of this file as in gate_gemm.hip: every
-// function carries LP_FN, helpers are this file's own or builtins.
+// Packed-f32 VALU ops stay out of this file: every function carries NOPK_FN,
+// helpers are drla_nopk.h's (which says why), this file's own or builtins.
 
 #include "drla_kernels.h"
-#include "conv_wgrad_lds.h"
-
-#define LP_FN __attribute__((target("no-packed-fp32-ops")))
-#define LP_INL LP_FN __device__ __forceinline__
-#define LP_LAMBDA \
-  __attribute__((always_inline, target("no-packed-fp32-ops")))
-#define LP_PRE extern "C" LP_FN __launch_bounds__(DRLA_LP_BLOCK)
+#include "drla_nopk.h"
 
 namespace {
 
 constexpr int LP_T = DRLA_LP_TILE;        // tile edge and chunk depth
-constexpr int LP_PITCH = (LP_T + 8) * 2;  // bytes per k-contiguous LDS row
-constexpr int LP_KC = LP_T * LP_PITCH;    // one k-contiguous tile
-constexpr int LP_ROWB = 128;              // k-rows image: 64 columns
-constexpr int LP_KR = DRLA_WG_ROWS * LP_ROWB;
-static_assert(LP_T == 64 && LP_T == DRLA_WG_ROWS && DRLA_LP_BLOCK == 256,
-              "the k-rows image of conv_wgrad_lds.h is 64 k x 64 columns, "
-              "staged by 256 threads in two passes");
-static_assert((LP_PITCH / 16) % 2 == 1,
-              "odd pitch in 16-byte units: fragment reads spread over banks");
-
-typedef __attribute__((ext_vector_type(2))) float lp_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 lp_bf16x2;
-typedef __attribute__((ext_vector_type(4))) short lp_s16x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int lp_u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int lp_u32x4;
-
-LP_INL void lp_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-LP_INL int lp_min(int a, int b) { return a < b ? a : b; }
-LP_INL float lp_f32(bf16raw u) {
-  return __builtin_bit_cast(float, (unsigned int)u << 16);
-}
-// two f32 -> packed bf16, round to nearest even: one v_cvt_pk_bf16_f32
-LP_INL unsigned int lp_round2(float a, float b) {
-  return __builtin_bit_cast(
-      unsigned int, __builtin_convertvector(lp_f32x2{a, b}, lp_bf16x2));
-}
-LP_INL lp_u32x2 lp_round4(f32x4 v) {
-  return lp_u32x2{lp_round2(v[0], v[1]), lp_round2(v[2], v[3])};
-}
-
-// drla_wg_chunk_off<128> / drla_wg_tr_off<128> / drla_wg_elem_off<128> at run
-// time. The header's constexpr functions are not always_inline, so they are
-// restated here under LP_FN and held equal to them at compile time.
-LP_INL constexpr int lp_chunk_off(int row, int ch) {
-  const int sw = (row & 1) | (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2);
-  return LP_ROWB * row + 16 * (ch ^ sw);
-}
-LP_INL constexpr int lp_tr_off(int lane, int tile) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  return lp_chunk_off(8 * g + q, 2 * tile + (p >> 1)) + 8 * (p & 1);
-}
-LP_INL constexpr int lp_elem_off(int row, int col) {
-  return lp_chunk_off(row, col >> 3) + 2 * (col & 7);
-}
-constexpr bool lp_maps_match_header() {
-  for (int row = 0; row < DRLA_WG_ROWS; ++row) {
-    for (int ch = 0; ch < 8; ++ch)
-      if (lp_chunk_off(row, ch) != drla_wg_chunk_off<LP_ROWB>(row, ch))
-        return false;
-    for (int col = 0; col < 64; ++col)
-      if (lp_elem_off(row, col) != drla_wg_elem_off<LP_ROWB>(row, col))
-        return false;
-  }
-  for (int lane = 0; lane < 64; ++lane)
-    for (int tile = 0; tile < 4; ++tile)
-      if (lp_tr_off(lane, tile) != drla_wg_tr_off<LP_ROWB>(lane, tile))
-        return false;
-  // the staging slot of this file: row tid / 8 + 32 j, chunk tid % 8
-  for (int tid = 0; tid < DRLA_LP_BLOCK; ++tid)
-    for (int j = 0; j < 2; ++j) {
-      const DrlaWgSlot s = drla_wg_b_slot<64>(tid, j);
-      if (s.row != (tid >> 3) + 32 * j || s.ch != (tid & 7)) return false;
-    }
-  return true;
-}
-static_assert(lp_maps_match_header(),
-              "the k-rows maps and slot are those conv_wgrad_lds.h proves");
-
-// registers -> LDS, pass j of this thread's slot
-LP_INL void lp_stage_kc(unsigned char* lds, int tid, int j, bf16x8 v) {
-  *reinterpret_cast<bf16x8*>(lds + ((tid >> 3) + 32 * j) * LP_PITCH +
-                             16 * (tid & 7)) = v;
-}
-LP_INL void lp_stage_kr(unsigned char* lds, int tid, int j, bf16x8 v) {
-  *reinterpret_cast<bf16x8*>(lds + lp_chunk_off((tid >> 3) + 32 * j,
-                                                tid & 7)) = v;
-}
-// 16x16x32 operand of 16-wide tile t16, k-step ks: lane l gets element
-// (16 t16 + l % 16, 32 ks + 8 (l / 16) + e) in e = 0..7
-LP_INL bf16x8 lp_frag_kc(const unsigned char* lds, int t16, int ks, int lane) {
-  return *reinterpret_cast<const bf16x8*>(
-      lds + (t16 * 16 + (lane & 15)) * LP_PITCH + 64 * ks + 16 * (lane >> 4));
-}
-// EXEC is full at every call
-LP_INL bf16x8 lp_frag_kr(const unsigned char* lds, int t16, int ks, int lane) {
-  typedef __attribute__((address_space(3))) lp_s16x4* lds_ptr;
-  const unsigned char* q = lds + lp_tr_off(lane, t16) + 32 * ks * LP_ROWB;
-  const lp_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)q);
-  const lp_s16x4 hi =
-      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(q + 4 * LP_ROWB));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+static_assert(LP_T == NOPK_BK && DRLA_LP_BLOCK == 256,
+              "the tiles of drla_nopk.h: 64 k x 64 columns, staged by 256 "
+              "threads in two passes");
 
 // A [rows][ld] bf16 matrix read in 16-byte pieces, for one 64 x 64 tile whose
 // second index (the contiguous one) starts at c0. As a k-contiguous operand
@@ -172,20 +73,20 @@ struct LpPiece {
 
   // rows r0 + srow + 32 j, columns c0 + 8 sch .. + 7 of p [nrows][ld] with
   // ncols columns (a multiple of 8, at least 8; nrows at least 1)
-  LP_INL void load(const bf16raw* __restrict__ p, long long ld, int r0,
+  NOPK_INL void load(const bf16raw* __restrict__ p, long long ld, int r0,
                    int nrows, int c0, int ncols, int tid) {
     const int c = c0 + 8 * (tid & 7);
-    const long long coff = lp_min(c, ncols - 8);
+    const long long coff = nopk_min(c, ncols - 8);
     live = 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int row = r0 + (tid >> 3) + 32 * j;
       live |= (unsigned int)(row < nrows && c < ncols) << j;
       r[j] = *reinterpret_cast<const bf16x8*>(
-          p + (long long)lp_min(row, nrows - 1) * ld + coff);
+          p + (long long)nopk_min(row, nrows - 1) * ld + coff);
     }
   }
-  LP_INL bf16x8 get(int j) const {
+  NOPK_INL bf16x8 get(int j) const {
     const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
     return ((live >> j) & 1u) ? r[j] : z;
   }
@@ -193,7 +94,7 @@ struct LpPiece {
 
 // the epilogue all three products share: wave's 16-row tile, lane's row
 // l % 16 and four columns 4 (l / 16) .. + 3 of each 16-column tile
-LP_INL void lp_store_bf16(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
+NOPK_INL void lp_store_bf16(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
                           long long ldc, int m0, int mmax, int n0, int nmax,
                           int wave, int lane) {
   const int m = m0 + 16 * wave + (lane & 15);
@@ -201,8 +102,8 @@ LP_INL void lp_store_bf16(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
   for (int ni = 0; ni < 4; ++ni) {
     const int n = n0 + 16 * ni + 4 * (lane >> 4);
     if (m < mmax && n < nmax) {  // nmax % 8 == 0: four columns in or out
-      *reinterpret_cast<lp_u32x2*>(c + (long long)m * ldc + n) =
-          lp_round4(acc[ni]);
+      *reinterpret_cast<nopk_u32x2*>(c + (long long)m * ldc + n) =
+          nopk_round4(acc[ni]);
     }
   }
 }
@@ -211,13 +112,13 @@ LP_INL void lp_store_bf16(const f32x4 (&acc)[4], bf16raw* __restrict__ c,
 
 // grid (ceil(N / 64), ceil(M / 64), S). conv [M][F1] (row stride ldc), emb
 // [M][F2] (lde), w [F1 + F2 ..][N] (ldw) -> ws [S][M][N] f32
-LP_PRE __global__ void drla_lstm_proj_fwd(
+NOPK_PRE(DRLA_LP_BLOCK) __global__ void drla_lstm_proj_fwd(
     const bf16raw* __restrict__ conv, long long ldc,
     const bf16raw* __restrict__ emb, long long lde,
     const bf16raw* __restrict__ w, long long ldw, float* __restrict__ ws,
     int M, int F1, int F2, int N) {
-  __shared__ __attribute__((aligned(16))) unsigned char As[2][LP_KC];
-  __shared__ __attribute__((aligned(16))) unsigned char Bs[2][LP_KR];
+  __shared__ __attribute__((aligned(16))) unsigned char As[2][NOPK_KC_SUB];
+  __shared__ __attribute__((aligned(16))) unsigned char Bs[2][NOPK_KR_SUB];
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int n0 = blockIdx.x * LP_T, m0 = blockIdx.y * LP_T;
@@ -225,8 +126,8 @@ LP_PRE __global__ void drla_lstm_proj_fwd(
   const int nc1 = F1 / LP_T;
   const int chunks = nc1 + (F2 + LP_T - 1) / LP_T;
   const int per = (chunks + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int c_begin = lp_min((int)blockIdx.z * per, chunks);
-  const int nchunks = lp_min(c_begin + per, chunks) - c_begin;
+  const int c_begin = nopk_min((int)blockIdx.z * per, chunks);
+  const int nchunks = nopk_min(c_begin + per, chunks) - c_begin;
 
   f32x4 acc[4];
 #pragma unroll
@@ -235,8 +136,8 @@ LP_PRE __global__ void drla_lstm_proj_fwd(
   LpPiece pa, pb;
   // chunk c of the whole product; past the last one the addresses are the
   // last chunk's and the registers are never staged
-  auto load = [&](int c) LP_LAMBDA {
-    c = lp_min(c, chunks - 1);
+  auto load = [&](int c) NOPK_LAMBDA {
+    c = nopk_min(c, chunks - 1);
     if (c < nc1) {  // block-uniform
       pa.load(conv, ldc, m0, M, LP_T * c, F1, tid);
     } else {
@@ -244,11 +145,11 @@ LP_PRE __global__ void drla_lstm_proj_fwd(
     }
     pb.load(w, ldw, LP_T * c, F, n0, N, tid);
   };
-  auto stage = [&](int buf) LP_LAMBDA {
+  auto stage = [&](int buf) NOPK_LAMBDA {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      lp_stage_kc(As[buf], tid, j, pa.get(j));
-      lp_stage_kr(Bs[buf], tid, j, pb.get(j));
+      nopk_stage_kc(As[buf], tid, j, pa.get(j));
+      nopk_stage_kr(Bs[buf], tid, j, pb.get(j));
     }
   };
 
@@ -256,7 +157,7 @@ LP_PRE __global__ void drla_lstm_proj_fwd(
     load(c_begin);
     stage(0);
     load(c_begin + 1);
-    lp_barrier();
+    nopk_barrier();
 #pragma unroll 1
     for (int t = 0; t < nchunks; ++t) {
       const int cur = t & 1;
@@ -266,15 +167,15 @@ LP_PRE __global__ void drla_lstm_proj_fwd(
       }
 #pragma unroll
       for (int ks = 0; ks < LP_T / 32; ++ks) {
-        const bf16x8 af = lp_frag_kc(As[cur], wave, ks, lane);
+        const bf16x8 af = nopk_frag_kc(As[cur], NOPK_PITCH, wave, ks, lane);
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           // B first: D[n][m], a lane holds n = 4 (l / 16) .. + 3 of m = l % 16
           acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              lp_frag_kr(Bs[cur], ni, ks, lane), af, acc[ni], 0, 0, 0);
+              nopk_frag_kr(Bs[cur], ni, ks, lane), af, acc[ni], 0, 0, 0);
         }
       }
-      lp_barrier();
+      nopk_barrier();
     }
   }
 
@@ -289,39 +190,21 @@ LP_PRE __global__ void drla_lstm_proj_fwd(
   }
 }
 
-// xg[i] = bf16(ws[0][i] + .. + ws[S-1][i] + bias[i % N]), four outputs per
-// thread and step; n4 = M * N / 4, N % 4 == 0
-LP_PRE __global__ void drla_lstm_proj_reduce(const float* __restrict__ ws,
-                                             const bf16raw* __restrict__ bias,
-                                             bf16raw* __restrict__ xg,
-                                             long long n4, int N, int S) {
-  const long long stride = (long long)gridDim.x * DRLA_LP_BLOCK;
-  for (long long i = (long long)blockIdx.x * DRLA_LP_BLOCK + threadIdx.x;
-       i < n4; i += stride) {
-    f32x4 sum = *reinterpret_cast<const f32x4*>(ws + 4 * i);
-    for (int s = 1; s < S; ++s) {
-      const f32x4 v =
-          *reinterpret_cast<const f32x4*>(ws + 4 * ((long long)s * n4 + i));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sum[e] += v[e];
-    }
-    // M * N < 2^31 (launcher): 32-bit remainder
-    const ushort4v b = *reinterpret_cast<const ushort4v*>(
-        bias + (unsigned int)(4 * i) % (unsigned int)N);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sum[e] += lp_f32(b[e]);
-    *reinterpret_cast<lp_u32x2*>(xg + 4 * i) = lp_round4(sum);
-  }
+// xg[i] = bf16(ws[0][i] + .. + ws[S-1][i] + bias[i % N]); n4 = M * N / 4
+NOPK_PRE(DRLA_LP_BLOCK) __global__ void drla_lstm_proj_reduce(
+    const float* __restrict__ ws, const bf16raw* __restrict__ bias,
+    bf16raw* __restrict__ xg, long long n4, int N, int S) {
+  nopk_split_reduce<DRLA_LP_BLOCK, true>(ws, bias, xg, n4, N, S);
 }
 
 // grid (F1 / 64 + ceil(F2 / 64), ceil(M / 64)). dxg [M][N] (lddg), w (ldw)
 // -> dconv [M][F1], demb [M][F2], both dense
-LP_PRE __global__ void drla_lstm_proj_dgrad(
+NOPK_PRE(DRLA_LP_BLOCK) __global__ void drla_lstm_proj_dgrad(
     const bf16raw* __restrict__ dxg, long long lddg,
     const bf16raw* __restrict__ w, long long ldw, bf16raw* __restrict__ dconv,
     bf16raw* __restrict__ demb, int M, int F1, int F2, int N) {
-  __shared__ __attribute__((aligned(16))) unsigned char As[2][LP_KC];
-  __shared__ __attribute__((aligned(16))) unsigned char Bs[2][LP_KC];
+  __shared__ __attribute__((aligned(16))) unsigned char As[2][NOPK_KC_SUB];
+  __shared__ __attribute__((aligned(16))) unsigned char Bs[2][NOPK_KC_SUB];
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int f0 = blockIdx.x * LP_T, m0 = blockIdx.y * LP_T;
@@ -333,23 +216,23 @@ LP_PRE __global__ void drla_lstm_proj_dgrad(
   for (int ni = 0; ni < 4; ++ni) acc[ni] = {0.f, 0.f, 0.f, 0.f};
 
   LpPiece pa, pb;
-  auto load = [&](int c) LP_LAMBDA {
-    c = lp_min(c, nchunks - 1);
+  auto load = [&](int c) NOPK_LAMBDA {
+    c = nopk_min(c, nchunks - 1);
     pa.load(dxg, lddg, m0, M, LP_T * c, N, tid);
     pb.load(w, ldw, f0, F, LP_T * c, N, tid);
   };
-  auto stage = [&](int buf) LP_LAMBDA {
+  auto stage = [&](int buf) NOPK_LAMBDA {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      lp_stage_kc(As[buf], tid, j, pa.get(j));
-      lp_stage_kc(Bs[buf], tid, j, pb.get(j));
+      nopk_stage_kc(As[buf], tid, j, pa.get(j));
+      nopk_stage_kc(Bs[buf], tid, j, pb.get(j));
     }
   };
 
   load(0);
   stage(0);
   load(1);
-  lp_barrier();
+  nopk_barrier();
 #pragma unroll 1
   for (int t = 0; t < nchunks; ++t) {
     const int cur = t & 1;
@@ -359,14 +242,14 @@ LP_PRE __global__ void drla_lstm_proj_dgrad(
     }
 #pragma unroll
     for (int ks = 0; ks < LP_T / 32; ++ks) {
-      const bf16x8 af = lp_frag_kc(As[cur], wave, ks, lane);
+      const bf16x8 af = nopk_frag_kc(As[cur], NOPK_PITCH, wave, ks, lane);
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            lp_frag_kc(Bs[cur], ni, ks, lane), af, acc[ni], 0, 0, 0);
+            nopk_frag_kc(Bs[cur], NOPK_PITCH, ni, ks, lane), af, acc[ni], 0, 0, 0);
       }
     }
-    lp_barrier();
+    nopk_barrier();
   }
 
   if (f0 < F1) {  // block-uniform: the tile is dconv's or demb's
@@ -378,14 +261,14 @@ LP_PRE __global__ void drla_lstm_proj_dgrad(
 
 // grid ceil((F + H) / 64) * ceil(N / 64). conv [M][F1] (ldc), emb [M][F2]
 // (lde), hprev [M][H] dense, dxg [M][N] (lddg) -> dw [F + H][N], db [N]
-LP_PRE __global__ void drla_lstm_proj_wgrad(
+NOPK_PRE(DRLA_LP_BLOCK) __global__ void drla_lstm_proj_wgrad(
     const bf16raw* __restrict__ conv, long long ldc,
     const bf16raw* __restrict__ emb, long long lde,
     const bf16raw* __restrict__ hprev, const bf16raw* __restrict__ dxg,
     long long lddg, bf16raw* __restrict__ dw, bf16raw* __restrict__ db, int M,
     int F1, int F2, int H, int N) {
-  __shared__ __attribute__((aligned(16))) unsigned char As[2][LP_KR];
-  __shared__ __attribute__((aligned(16))) unsigned char Bs[2][LP_KR];
+  __shared__ __attribute__((aligned(16))) unsigned char As[2][NOPK_KR_SUB];
+  __shared__ __attribute__((aligned(16))) unsigned char Bs[2][NOPK_KR_SUB];
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int nct = (N + LP_T - 1) / LP_T;
@@ -410,7 +293,7 @@ LP_PRE __global__ void drla_lstm_proj_wgrad(
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     hlive |= (unsigned int)(from_h && hc + 2 * e < H) << e;
-    const int c = lp_min(hc + 2 * e, H - 2);
+    const int c = nopk_min(hc + 2 * e, H - 2);
     hoff[e] = c < 0 ? 0 : c;
   }
 
@@ -420,16 +303,16 @@ LP_PRE __global__ void drla_lstm_proj_wgrad(
   float bsum = 0.f;
 
   LpPiece pa, pb;
-  auto load = [&](int c) LP_LAMBDA {
-    c = lp_min(c, nchunks - 1);
+  auto load = [&](int c) NOPK_LAMBDA {
+    c = nopk_min(c, nchunks - 1);
     if (from_h) {
       pa.live = 0;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int row = LP_T * c + (tid >> 3) + 32 * j;
         pa.live |= (unsigned int)(row < M) << j;
-        const bf16raw* q = hprev + (long long)lp_min(row, M - 1) * H;
-        lp_u32x4 v;
+        const bf16raw* q = hprev + (long long)nopk_min(row, M - 1) * H;
+        nopk_u32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const unsigned int u =
@@ -443,18 +326,18 @@ LP_PRE __global__ void drla_lstm_proj_wgrad(
     }
     pb.load(dxg, lddg, LP_T * c, M, n0, N, tid);
   };
-  auto stage = [&](int buf) LP_LAMBDA {
+  auto stage = [&](int buf) NOPK_LAMBDA {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      lp_stage_kr(As[buf], tid, j, pa.get(j));
-      lp_stage_kr(Bs[buf], tid, j, pb.get(j));
+      nopk_stage_kr(As[buf], tid, j, pa.get(j));
+      nopk_stage_kr(Bs[buf], tid, j, pb.get(j));
     }
   };
 
   load(0);
   stage(0);
   load(1);
-  lp_barrier();
+  nopk_barrier();
 #pragma unroll 1
   for (int t = 0; t < nchunks; ++t) {
     const int cur = t & 1;
@@ -464,25 +347,25 @@ LP_PRE __global__ void drla_lstm_proj_wgrad(
     }
 #pragma unroll
     for (int ks = 0; ks < LP_T / 32; ++ks) {
-      const bf16x8 af = lp_frag_kr(As[cur], wave, ks, lane);
+      const bf16x8 af = nopk_frag_kr(As[cur], wave, ks, lane);
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            lp_frag_kr(Bs[cur], ni, ks, lane), af, acc[ni], 0, 0, 0);
+            nopk_frag_kr(Bs[cur], ni, ks, lane), af, acc[ni], 0, 0, 0);
       }
     }
     if (with_db && wave == 0) {  // uniform: lane = column, rows in order
 #pragma unroll 16
       for (int r = 0; r < LP_T; ++r) {
-        bsum += lp_f32(*reinterpret_cast<const bf16raw*>(
-            Bs[cur] + lp_elem_off(r, lane)));
+        bsum += nopk_f32(*reinterpret_cast<const bf16raw*>(
+            Bs[cur] + nopk_elem_off(r, lane)));
       }
     }
-    lp_barrier();
+    nopk_barrier();
   }
 
   lp_store_bf16(acc, dw, N, r0, R, n0, N, wave, lane);
   if (with_db && wave == 0 && n0 + lane < N) {
-    db[n0 + lane] = (bf16raw)(lp_round2(bsum, 0.f) & 0xffffu);
+    db[n0 + lane] = (bf16raw)(nopk_round2(bsum, 0.f) & 0xffffu);
   }
 }

@@ -36,16 +36,12 @@
 // no atomics, no scratch buffer: run-to-run deterministic.
 //
 // Pieces outside a matrix are loaded from a clamped address and staged as
-// zeros; stores are predicated. Packed-f32 VALU ops stay out of this file as
-// in maxpool.hip: every function carries R2H_FN, helpers are this file's own
-// or always-inline builtins.
+// zeros; stores are predicated. Packed-f32 VALU ops stay out of this file:
+// every function carries NOPK_FN, helpers are drla_nopk.h's (which says why),
+// this file's own or builtins.
 
 #include "drla_kernels.h"
-#include "conv_wgrad_lds.h"
-
-#define R2H_FN __attribute__((target("no-packed-fp32-ops")))
-#define R2H_INL R2H_FN __device__ __forceinline__
-#define R2H_PRE(threads) extern "C" R2H_FN __launch_bounds__(threads)
+#include "drla_nopk.h"
 
 namespace {
 
@@ -55,8 +51,6 @@ constexpr int R2H_MAX_KS = DRLA_R2H_MAX_H / 32;  // layer-1 k-steps
 constexpr int R2H_H_LD = DRLA_R2H_MAX_H + 8;     // hb rows, elements
 constexpr int R2H_Z_LD = R2H_MID + 8;            // z / dz rows, elements
 constexpr int R2H_DY_LD = DRLA_R2H_DY_LD + 8;    // dy rows in LDS, elements
-constexpr int R2H_ROWB = 128;                    // k-rows image: 64 columns
-constexpr int R2H_IMG = DRLA_WG_ROWS * R2H_ROWB;
 static_assert(DRLA_R2H_BLOCK == 256 && R2H_BM == 16 && R2H_MID == 128 &&
                   DRLA_R2H_DY_LD == 64 && DRLA_R2H_MAX_AO == 64,
               "four waves: 32 trunk columns each, one 16-row out tile each; "
@@ -64,91 +58,6 @@ static_assert(DRLA_R2H_BLOCK == 256 && R2H_BM == 16 && R2H_MID == 128 &&
 static_assert((R2H_H_LD * 2 / 16) % 2 == 1 && (R2H_Z_LD * 2 / 16) % 2 == 1 &&
                   (R2H_DY_LD * 2 / 16) % 2 == 1,
               "odd pitch in 16-byte units: fragment reads spread over banks");
-
-typedef __attribute__((ext_vector_type(2))) float r2h_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 r2h_bf16x2;
-typedef __attribute__((ext_vector_type(4))) short r2h_s16x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int r2h_u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int r2h_u32x4;
-
-R2H_INL void r2h_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-R2H_INL int r2h_min(int a, int b) { return a < b ? a : b; }
-R2H_INL float r2h_f32(bf16raw u) {
-  return __builtin_bit_cast(float, (unsigned int)u << 16);
-}
-// two f32 -> packed bf16, round to nearest even: one v_cvt_pk_bf16_f32
-R2H_INL unsigned int r2h_round2(float a, float b) {
-  return __builtin_bit_cast(
-      unsigned int, __builtin_convertvector(r2h_f32x2{a, b}, r2h_bf16x2));
-}
-R2H_INL r2h_u32x2 r2h_round4(f32x4 v) {
-  return r2h_u32x2{r2h_round2(v[0], v[1]), r2h_round2(v[2], v[3])};
-}
-R2H_INL bf16raw r2h_round1(float a) {
-  return (bf16raw)(r2h_round2(a, a) & 0xffffu);
-}
-// eight f32 -> the 16-byte bf16 chunk the forward stages and wgrad restages
-R2H_INL bf16x8 r2h_round8(f32x4 lo, f32x4 hi) {
-  const r2h_u32x4 p = {r2h_round2(lo[0], lo[1]), r2h_round2(lo[2], lo[3]),
-                       r2h_round2(hi[0], hi[1]), r2h_round2(hi[2], hi[3])};
-  return __builtin_bit_cast(bf16x8, p);
-}
-R2H_INL float r2h_relu(float v) { return v > 0.f ? v : 0.f; }
-// a bf16 value is > 0 iff its bits, read as a signed short, are
-R2H_INL bool r2h_pos(bf16raw u) { return (short)u > 0; }
-R2H_INL bf16x8 r2h_zero8() { return bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
-
-// drla_wg_chunk_off<128> / drla_wg_elem_off<128> / drla_wg_tr_off<128> at run
-// time, restated under R2H_FN (the header's functions are not always_inline)
-// and held equal to them for every argument at compile time
-R2H_INL constexpr int r2h_chunk_off(int row, int ch) {
-  const int sw = (row & 1) | (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2);
-  return R2H_ROWB * row + 16 * (ch ^ sw);
-}
-R2H_INL constexpr int r2h_elem_off(int row, int col) {
-  return r2h_chunk_off(row, col >> 3) + 2 * (col & 7);
-}
-R2H_INL constexpr int r2h_tr_off(int lane, int tile) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  return r2h_chunk_off(8 * g + q, 2 * tile + (p >> 1)) + 8 * (p & 1);
-}
-constexpr bool r2h_maps_match_header() {
-  for (int row = 0; row < DRLA_WG_ROWS; ++row)
-    for (int col = 0; col < 64; ++col)
-      if (r2h_elem_off(row, col) != drla_wg_elem_off<R2H_ROWB>(row, col) ||
-          r2h_chunk_off(row, col >> 3) !=
-              drla_wg_chunk_off<R2H_ROWB>(row, col >> 3))
-        return false;
-  for (int lane = 0; lane < 64; ++lane)
-    for (int tile = 0; tile < 4; ++tile)
-      if (r2h_tr_off(lane, tile) != drla_wg_tr_off<R2H_ROWB>(lane, tile))
-        return false;
-  return true;
-}
-static_assert(r2h_maps_match_header(),
-              "the k-rows maps are those conv_wgrad_lds.h proves");
-
-// 16x16x32 operand out of a k-rows image: lane l gets element (column
-// 16 tile + l % 16, k-row 32 ks + 8 (l / 16) + e) in e = 0..7. EXEC is full.
-R2H_INL bf16x8 r2h_tr_frag(const unsigned char* img, int tile, int ks,
-                           int lane) {
-  typedef __attribute__((address_space(3))) r2h_s16x4* lds_ptr;
-  const unsigned char* q = img + r2h_tr_off(lane, tile) + 32 * ks * R2H_ROWB;
-  const r2h_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)q);
-  const r2h_s16x4 hi =
-      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(q + 4 * R2H_ROWB));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-// 16x16x32 operand out of k-contiguous rows of ld elements: lane l gets
-// element (row l % 16, k 32 ks + 8 (l / 16) + e)
-R2H_INL bf16x8 r2h_kc_frag(const bf16raw* rows, int ld, int ks, int lane) {
-  return *reinterpret_cast<const bf16x8*>(rows + (lane & 15) * ld + 32 * ks +
-                                          8 * (lane >> 4));
-}
 
 // A thread's share of one 64 k-row x 64 column image of a bf16 matrix:
 // rows srow and srow + 32, chunk sch (drla_wg_b_slot<64>)
@@ -158,7 +67,7 @@ struct R2hPiece {
 };
 // k-rows k0 + .. of a [kmax][ld] matrix, columns c0 + 8 sch .. + 7 of cmax
 // (a multiple of 8)
-R2H_INL void r2h_load_bf16(R2hPiece& p, const bf16raw* __restrict__ m,
+NOPK_INL void r2h_load_bf16(R2hPiece& p, const bf16raw* __restrict__ m,
                            long long ld, int k0, int kmax, int c0, int cmax,
                            int tid) {
   const int srow = tid >> 3, c = c0 + 8 * (tid & 7);
@@ -168,11 +77,11 @@ R2H_INL void r2h_load_bf16(R2hPiece& p, const bf16raw* __restrict__ m,
     const int k = k0 + srow + 32 * j;
     p.live |= (unsigned int)(k < kmax && c < cmax) << j;
     p.r[j] = *reinterpret_cast<const bf16x8*>(
-        m + (long long)r2h_min(k, kmax - 1) * ld + r2h_min(c, cmax - 8));
+        m + (long long)nopk_min(k, kmax - 1) * ld + nopk_min(c, cmax - 8));
   }
 }
 // the same out of an f32 matrix, rounded as the forward rounds h
-R2H_INL void r2h_load_f32(R2hPiece& p, const float* __restrict__ m,
+NOPK_INL void r2h_load_f32(R2hPiece& p, const float* __restrict__ m,
                           long long ld, int k0, int kmax, int c0, int cmax,
                           int tid) {
   const int srow = tid >> 3, c = c0 + 8 * (tid & 7);
@@ -182,20 +91,18 @@ R2H_INL void r2h_load_f32(R2hPiece& p, const float* __restrict__ m,
   for (int j = 0; j < 2; ++j) {
     const int k = k0 + srow + 32 * j;
     p.live |= (unsigned int)(k < kmax && c < cmax) << j;
-    const float* s = m + (long long)r2h_min(k, kmax - 1) * ld +
-                     r2h_min(c, cmax - 8);
+    const float* s = m + (long long)nopk_min(k, kmax - 1) * ld +
+                     nopk_min(c, cmax - 8);
     lo[j] = *reinterpret_cast<const f32x4*>(s);
     hi[j] = *reinterpret_cast<const f32x4*>(s + 4);
   }
 #pragma unroll
-  for (int j = 0; j < 2; ++j) p.r[j] = r2h_round8(lo[j], hi[j]);
+  for (int j = 0; j < 2; ++j) p.r[j] = nopk_round8(lo[j], hi[j]);
 }
-R2H_INL void r2h_store_piece(const R2hPiece& p, unsigned char* img, int tid) {
+NOPK_INL void r2h_store_piece(const R2hPiece& p, unsigned char* img, int tid) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    *reinterpret_cast<bf16x8*>(img +
-                               r2h_chunk_off((tid >> 3) + 32 * j, tid & 7)) =
-        (p.live >> j) & 1u ? p.r[j] : r2h_zero8();
+    nopk_stage_kr(img, tid, j, (p.live >> j) & 1u ? p.r[j] : nopk_zero8());
   }
 }
 
@@ -206,7 +113,7 @@ R2H_INL void r2h_store_piece(const R2hPiece& p, unsigned char* img, int tid) {
 // grid ceil(N / 16), N = B W rows. h_all [B][L][H] f32, row n at (n / W,
 // burn + n % W); wt [128][H], bt [128], wo [A + 1][128], bo [A + 1] ->
 // q [N][A]; zs != null: also zs [N][128].
-R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
+NOPK_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
     const float* __restrict__ h_all, const bf16raw* __restrict__ wt,
     const bf16raw* __restrict__ bt, const bf16raw* __restrict__ wo,
     const bf16raw* __restrict__ bo, bf16raw* __restrict__ q,
@@ -232,7 +139,7 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
       for (int ni = 0; ni < 2; ++ni) {
         f1[ks][ni] = *reinterpret_cast<const bf16x8*>(
             wt + (long long)(32 * wave + 16 * ni + (lane & 15)) * H +
-            r2h_min(32 * ks + kq, H - 8));
+            nopk_min(32 * ks + kq, H - 8));
       }
     }
   }
@@ -250,11 +157,11 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
 #pragma unroll
     for (int kc = 0; kc < R2H_MID / 32; ++kc) {
       f2[kc] = *reinterpret_cast<const bf16x8*>(
-          wo + r2h_min(a_row, AO - 1) * R2H_MID + 32 * kc + kq);
+          wo + nopk_min(a_row, AO - 1) * R2H_MID + 32 * kc + kq);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      bias2[e] = bo[r2h_min(16 * wave + 4 * (lane >> 4) + e, AO - 1)];
+      bias2[e] = bo[nopk_min(16 * wave + 4 * (lane >> 4) + e, AO - 1)];
     }
   }
 
@@ -262,13 +169,13 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
   // the end of the last k-step is zeros
   {
     const int r = tid >> 4;
-    const int n = r2h_min(row0 + r, N - 1);
+    const int n = nopk_min(row0 + r, N - 1);
     const float* src =
         h_all + ((long long)(n / W) * L + burn + n % W) * (long long)H;
     f32x4 lo[4], hi[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int c = r2h_min((tid & 15) + 16 * j, H / 8 - 1);
+      const int c = nopk_min((tid & 15) + 16 * j, H / 8 - 1);
       lo[j] = *reinterpret_cast<const f32x4*>(src + 8 * c);
       hi[j] = *reinterpret_cast<const f32x4*>(src + 8 * c + 4);
     }
@@ -277,12 +184,12 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
       const int c = (tid & 15) + 16 * j;
       if (c < 4 * nks) {
         *reinterpret_cast<bf16x8*>(&hb[r][8 * c]) =
-            (8 * c < H && row0 + r < N) ? r2h_round8(lo[j], hi[j])
-                                        : r2h_zero8();
+            (8 * c < H && row0 + r < N) ? nopk_round8(lo[j], hi[j])
+                                        : nopk_zero8();
       }
     }
   }
-  r2h_barrier();
+  nopk_barrier();
 
   // layer 1: D[trunk column][row]
   const int row = lane & 15;
@@ -292,12 +199,12 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
 #pragma unroll
     for (int ks = 0; ks < R2H_MAX_KS; ++ks) {
       if (ks < nks) {
-        const bf16x8 bf = r2h_kc_frag(&hb[0][0], R2H_H_LD, ks, lane);
+        const bf16x8 bf = nopk_frag_kc(&hb[0][0], R2H_H_LD, 0, ks, lane);
         const bool k_in = 32 * ks + kq < H;
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
           acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              k_in ? f1[ks][ni] : r2h_zero8(), bf, acc[ni], 0, 0, 0);
+              k_in ? f1[ks][ni] : nopk_zero8(), bf, acc[ni], 0, 0, 0);
         }
       }
     }
@@ -307,41 +214,41 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[e] = r2h_relu(acc[ni][e] + r2h_f32(bias1[ni][e]));
+        v[e] = nopk_relu(acc[ni][e] + nopk_f32(bias1[ni][e]));
       }
-      const r2h_u32x2 z = r2h_round4(v);
-      *reinterpret_cast<r2h_u32x2*>(&zl[row][o]) = z;
+      const nopk_u32x2 z = nopk_round4(v);
+      *reinterpret_cast<nopk_u32x2*>(&zl[row][o]) = z;
       if (zs && row_in) {
-        *reinterpret_cast<r2h_u32x2*>(
+        *reinterpret_cast<nopk_u32x2*>(
             zs + (long long)(row0 + row) * R2H_MID + o) = z;
       }
     }
   }
-  r2h_barrier();
+  nopk_barrier();
 
   // layer 2: D[out row][row]; the mean row A goes to the other lanes by LDS
   f32x4 y = {0.f, 0.f, 0.f, 0.f};
   if (l2) {
 #pragma unroll
     for (int kc = 0; kc < R2H_MID / 32; ++kc) {
-      const bf16x8 bf = r2h_kc_frag(&zl[0][0], R2H_Z_LD, kc, lane);
+      const bf16x8 bf = nopk_frag_kc(&zl[0][0], R2H_Z_LD, 0, kc, lane);
       y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          a_row < AO ? f2[kc] : r2h_zero8(), bf, y, 0, 0, 0);
+          a_row < AO ? f2[kc] : nopk_zero8(), bf, y, 0, 0, 0);
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] += r2h_f32(bias2[e]);
+    for (int e = 0; e < 4; ++e) y[e] += nopk_f32(bias2[e]);
     if (wave == (A >> 4) && (lane >> 4) == ((A & 15) >> 2)) {
       const int e = A & 3;
       ym[row] = e == 0 ? y[0] : e == 1 ? y[1] : e == 2 ? y[2] : y[3];
     }
   }
-  r2h_barrier();
+  nopk_barrier();
   if (l2 && row_in) {
     const float m = ym[row];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int a = 16 * wave + 4 * (lane >> 4) + e;
-      if (a < A) q[(long long)(row0 + row) * A + a] = r2h_round1(y[e] - m);
+      if (a < A) q[(long long)(row0 + row) * A + a] = nopk_round1(y[e] - m);
     }
   }
 }
@@ -350,15 +257,15 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_fwd(
 
 // grid ceil(N / 16). dq [N][A], zs [N][128], wt [128][H], wo [A + 1][128] ->
 // dh [N][H] f32, dyg [N][64] (columns past A zero), dzg [N][128]
-R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
+NOPK_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
     const bf16raw* __restrict__ dq, const bf16raw* __restrict__ zs,
     const bf16raw* __restrict__ wt, const bf16raw* __restrict__ wo,
     float* __restrict__ dh, bf16raw* __restrict__ dyg,
     bf16raw* __restrict__ dzg, int N, int H, int A) {
   // Wt: [buffer][trunk rows 0..63 | 64..127] images of one 64-column block
-  __shared__ __attribute__((aligned(16))) unsigned char wti[2][2 * R2H_IMG];
+  __shared__ __attribute__((aligned(16))) unsigned char wti[2][2 * NOPK_KR_SUB];
   // Wo: [columns 0..63 | 64..127] images, k-rows = out rows (zero past A)
-  __shared__ __attribute__((aligned(16))) unsigned char woi[2 * R2H_IMG];
+  __shared__ __attribute__((aligned(16))) unsigned char woi[2 * NOPK_KR_SUB];
   __shared__ __attribute__((aligned(16))) bf16raw dyl[R2H_BM][R2H_DY_LD];
   __shared__ __attribute__((aligned(16))) bf16raw dzl[R2H_BM][R2H_Z_LD];
 
@@ -368,7 +275,7 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
   const int AO = A + 1;
   const int row = lane & 15;  // the row of this lane's accumulators
   const bool row_in = row0 + row < N;
-  const long long grow = r2h_min(row0 + row, N - 1);
+  const long long grow = nopk_min(row0 + row, N - 1);
   const int nkb = (H + 63) / 64;
 
   // every load that needs no result of this kernel, requested first
@@ -386,8 +293,8 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
   const bool sr_in = row0 + sr < N;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    dqv[e] = dq[(long long)r2h_min(row0 + sr, N - 1) * A +
-                r2h_min(sc + e, A - 1)];
+    dqv[e] = dq[(long long)nopk_min(row0 + sr, N - 1) * A +
+                nopk_min(sc + e, A - 1)];
   }
 
   // dy[:A] = dq, the rest of the 64 columns zero
@@ -401,15 +308,15 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    r2h_store_piece(wop[i], woi + i * R2H_IMG, tid);
-    r2h_store_piece(wtp[i], wti[0] + i * R2H_IMG, tid);
+    r2h_store_piece(wop[i], woi + i * NOPK_KR_SUB, tid);
+    r2h_store_piece(wtp[i], wti[0] + i * NOPK_KR_SUB, tid);
   }
   // the second column block of Wt travels during the dy and dz phases
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     r2h_load_bf16(wtp[i], wt, H, 64 * i, R2H_MID, 64, H, tid);
   }
-  r2h_barrier();
+  nopk_barrier();
   // dy[A] = -sum_a dq[a], f32 in index order, rounded to bf16
   if (tid < R2H_BM) {
     float s = 0.f;
@@ -417,11 +324,11 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
     for (int j = 0; j < DRLA_R2H_DY_LD / 8; ++j) {
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(&dyl[tid][8 * j]);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) s += r2h_f32((bf16raw)v[e]);
+      for (int e = 0; e < 8; ++e) s += nopk_f32((bf16raw)v[e]);
     }
-    dyl[tid][A] = r2h_round1(-s);
+    dyl[tid][A] = nopk_round1(-s);
   }
-  r2h_barrier();
+  nopk_barrier();
   if (sr_in) {
     *reinterpret_cast<ushort4v*>(
         dyg + (long long)(row0 + sr) * DRLA_R2H_DY_LD + sc) =
@@ -432,16 +339,16 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
   // columns 32 w .. 32 w + 31 = tiles 2 (w % 2), + 1 of image w / 2
   {
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    const unsigned char* img = woi + (wave >> 1) * R2H_IMG;
+    const unsigned char* img = woi + (wave >> 1) * NOPK_KR_SUB;
     const int nks = (AO + 31) / 32;
 #pragma unroll
     for (int ks = 0; ks < DRLA_R2H_DY_LD / 32; ++ks) {
       if (ks < nks) {  // uniform
-        const bf16x8 bf = r2h_kc_frag(&dyl[0][0], R2H_DY_LD, ks, lane);
+        const bf16x8 bf = nopk_frag_kc(&dyl[0][0], R2H_DY_LD, 0, ks, lane);
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
           acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              r2h_tr_frag(img, 2 * (wave & 1) + ni, ks, lane), bf, acc[ni], 0,
+              nopk_frag_kr(img, 2 * (wave & 1) + ni, ks, lane), bf, acc[ni], 0,
               0, 0);
         }
       }
@@ -452,23 +359,23 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[e] = r2h_pos(mask[ni][e]) ? acc[ni][e] : 0.f;
+        v[e] = nopk_pos(mask[ni][e]) ? acc[ni][e] : 0.f;
       }
-      const r2h_u32x2 r = r2h_round4(v);
-      *reinterpret_cast<r2h_u32x2*>(&dzl[row][o]) = r;
+      const nopk_u32x2 r = nopk_round4(v);
+      *reinterpret_cast<nopk_u32x2*>(&dzl[row][o]) = r;
       if (row_in) {
-        *reinterpret_cast<r2h_u32x2*>(dzg + grow * R2H_MID + o) = r;
+        *reinterpret_cast<nopk_u32x2*>(dzg + grow * R2H_MID + o) = r;
       }
     }
   }
-  r2h_barrier();
+  nopk_barrier();
 
   // dh = dz . Wt: D[h column][row], one 64-column block of Wt per round,
   // wave w its columns 16 w .. 16 w + 15
   bf16x8 dzf[R2H_MID / 32];
 #pragma unroll
   for (int kc = 0; kc < R2H_MID / 32; ++kc) {
-    dzf[kc] = r2h_kc_frag(&dzl[0][0], R2H_Z_LD, kc, lane);
+    dzf[kc] = nopk_frag_kc(&dzl[0][0], R2H_Z_LD, 0, kc, lane);
   }
 #pragma unroll 1
   for (int t = 0; t < nkb; ++t) {
@@ -476,7 +383,7 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
     if (t + 1 < nkb) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        r2h_store_piece(wtp[i], wti[1 - cur] + i * R2H_IMG, tid);
+        r2h_store_piece(wtp[i], wti[1 - cur] + i * NOPK_KR_SUB, tid);
         r2h_load_bf16(wtp[i], wt, H, 64 * i, R2H_MID, 64 * (t + 2), H, tid);
       }
     }
@@ -484,14 +391,14 @@ R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_bwd(
 #pragma unroll
     for (int kc = 0; kc < R2H_MID / 32; ++kc) {
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          r2h_tr_frag(wti[cur] + (kc >> 1) * R2H_IMG, wave, kc & 1, lane),
+          nopk_frag_kr(wti[cur] + (kc >> 1) * NOPK_KR_SUB, wave, kc & 1, lane),
           dzf[kc], acc, 0, 0, 0);
     }
     const int k = 64 * t + 16 * wave + 4 * (lane >> 4);
     if (row_in && k < H) {
       *reinterpret_cast<f32x4*>(dh + grow * H + k) = acc;
     }
-    r2h_barrier();
+    nopk_barrier();
   }
 }
 
@@ -499,7 +406,7 @@ namespace {
 
 // the b operand of a weight-gradient tile: bf16 or f32 [N][ld]
 template <bool B_F32>
-R2H_INL void r2h_load_b(R2hPiece& p, const void* __restrict__ b, int ld,
+NOPK_INL void r2h_load_b(R2hPiece& p, const void* __restrict__ b, int ld,
                         int k0, int N, int n0, int nmax, int tid) {
   if constexpr (B_F32) {
     r2h_load_f32(p, static_cast<const float*>(b), ld, k0, N, n0, nmax, tid);
@@ -514,14 +421,14 @@ R2H_INL void r2h_load_b(R2hPiece& p, const void* __restrict__ b, int ld,
 // columns < nmax are stored. bias != null: also bias[m0 + i] = sum_n
 // a[n][m0 + i]. lds: [2 operands][2 buffers] images.
 template <bool B_F32>
-R2H_INL void r2h_wgrad_tile(unsigned char* lds, const bf16raw* __restrict__ a,
+NOPK_INL void r2h_wgrad_tile(unsigned char* lds, const bf16raw* __restrict__ a,
                             int lda, const void* __restrict__ b, int ldb,
                             int n0, int nmax, bf16raw* __restrict__ c, int m0,
                             int mmax, bf16raw* __restrict__ bias, int N) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   unsigned char* As = lds;
-  unsigned char* Bs = lds + 2 * R2H_IMG;
+  unsigned char* Bs = lds + 2 * NOPK_KR_SUB;
   R2hPiece pa, pb;
   f32x4 acc[4];
 #pragma unroll
@@ -535,36 +442,36 @@ R2H_INL void r2h_wgrad_tile(unsigned char* lds, const bf16raw* __restrict__ a,
   r2h_store_piece(pb, Bs, tid);
   r2h_load_bf16(pa, a, lda, DRLA_WG_ROWS, N, m0, lda, tid);
   r2h_load_b<B_F32>(pb, b, ldb, DRLA_WG_ROWS, N, n0, nmax, tid);
-  r2h_barrier();
+  nopk_barrier();
 #pragma unroll 1
   for (int t = 0; t < nchunks; ++t) {
     const int cur = t & 1;
     if (t + 1 < nchunks) {
       const int k0 = (t + 2) * DRLA_WG_ROWS;
-      r2h_store_piece(pa, As + (1 - cur) * R2H_IMG, tid);
-      r2h_store_piece(pb, Bs + (1 - cur) * R2H_IMG, tid);
+      r2h_store_piece(pa, As + (1 - cur) * NOPK_KR_SUB, tid);
+      r2h_store_piece(pb, Bs + (1 - cur) * NOPK_KR_SUB, tid);
       r2h_load_bf16(pa, a, lda, k0, N, m0, lda, tid);
       r2h_load_b<B_F32>(pb, b, ldb, k0, N, n0, nmax, tid);
     }
 #pragma unroll
     for (int ks = 0; ks < DRLA_WG_ROWS / 32; ++ks) {
-      const bf16x8 af = r2h_tr_frag(As + cur * R2H_IMG, wave, ks, lane);
+      const bf16x8 af = nopk_frag_kr(As + cur * NOPK_KR_SUB, wave, ks, lane);
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         // B first: D[n][m], a lane holds n = 4 (l / 16) .. + 3 of m = l % 16
         acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            r2h_tr_frag(Bs + cur * R2H_IMG, ni, ks, lane), af, acc[ni], 0, 0,
+            nopk_frag_kr(Bs + cur * NOPK_KR_SUB, ni, ks, lane), af, acc[ni], 0, 0,
             0);
       }
     }
     if (bias && wave == 0) {  // uniform: lane = column, rows in order
 #pragma unroll 16
       for (int r = 0; r < DRLA_WG_ROWS; ++r) {
-        bsum += r2h_f32(*reinterpret_cast<const bf16raw*>(
-            As + cur * R2H_IMG + r2h_elem_off(r, lane)));
+        bsum += nopk_f32(*reinterpret_cast<const bf16raw*>(
+            As + cur * NOPK_KR_SUB + nopk_elem_off(r, lane)));
       }
     }
-    r2h_barrier();
+    nopk_barrier();
   }
 
   const int m = m0 + 16 * wave + (lane & 15);
@@ -572,12 +479,12 @@ R2H_INL void r2h_wgrad_tile(unsigned char* lds, const bf16raw* __restrict__ a,
   for (int ni = 0; ni < 4; ++ni) {
     const int n = n0 + 16 * ni + 4 * (lane >> 4);
     if (m < mmax && n < nmax) {
-      *reinterpret_cast<r2h_u32x2*>(c + (long long)m * ldb + n) =
-          r2h_round4(acc[ni]);
+      *reinterpret_cast<nopk_u32x2*>(c + (long long)m * ldb + n) =
+          nopk_round4(acc[ni]);
     }
   }
   if (bias && wave == 0 && m0 + lane < mmax) {
-    bias[m0 + lane] = r2h_round1(bsum);
+    bias[m0 + lane] = nopk_round1(bsum);
   }
 }
 
@@ -585,13 +492,13 @@ R2H_INL void r2h_wgrad_tile(unsigned char* lds, const bf16raw* __restrict__ a,
 
 // grid 2 ceil(H / 64) + 2. h [N][H] f32, zs [N][128], dyg [N][64], dzg
 // [N][128] -> dwt [128][H], dbt [128], dwo [A + 1][128], dbo [A + 1]
-R2H_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_wgrad(
+NOPK_PRE(DRLA_R2H_BLOCK) __global__ void drla_r2h_wgrad(
     const float* __restrict__ h, const bf16raw* __restrict__ zs,
     const bf16raw* __restrict__ dyg, const bf16raw* __restrict__ dzg,
     bf16raw* __restrict__ dwt, bf16raw* __restrict__ dbt,
     bf16raw* __restrict__ dwo, bf16raw* __restrict__ dbo, int N, int H,
     int A) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * R2H_IMG];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * NOPK_KR_SUB];
   const int nk = (H + 63) / 64;
   const int job = blockIdx.x;
   if (job < 2 * nk) {  // block-uniform

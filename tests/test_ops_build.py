@@ -63,6 +63,23 @@ def test_missing_source_is_an_error_before_the_compiler_runs(monkeypatch):
         ops_build.build(verbose=False, force=False)
 
 
+# the kernel files that are compiled without the packed-f32 VALU ops
+NOPK_FILES = ["dueling_q.hip", "gate_gemm.hip", "heads_bwd.hip",
+              "lstm_proj.hip", "maxpool.hip", "r2d2_head.hip"]
+
+
+def test_no_packed_f32_attribute_lives_in_the_shared_header_only():
+    """The target attribute, and with it the helpers that must carry it, is
+    stated once: a new kernel file includes drla_nopk.h, it does not start
+    another copy."""
+    names = sorted(os.listdir(HIP_DIR))
+    holders = [n for n in names if "no-packed-fp32-ops" in _read(n)]
+    assert holders == ["drla_nopk.h"], holders
+    for name in NOPK_FILES:
+        assert re.search(r'^#include "drla_nopk\.h"$', _read(name), re.M), (
+            f"{name} does not include drla_nopk.h")
+
+
 def test_kernels_are_declared_in_one_header_only():
     hip = _hip_files(".hip")
     assert sorted(s for s in ops_build.SOURCES if s.endswith(".hip")) == hip
